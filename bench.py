@@ -12,18 +12,27 @@ ranks run the distributed drop-in (grid_amd/utils/dist_step4.py: files
 sliced over the ranks, all-to-all to column shards, RCCL collectives,
 offset-placed writer); steps 6-7 on rank 0.
 
-Beside it, in the same line:
+A plain run does only that: the cohort, W warmup runs, the K timed ones, the
+outputs with --dump-outputs, the result line.  With ``--full`` the same line
+also carries, each from runs of its own after the headline's:
   * device_chain: the device-resident chain of steps 4-7 (grid_amd/fused.py)
     on the same shape, the depth matrix generated in HBM before timing --
-    its Gram is the line's roofline (the metric's "k-NN distance vs peak");
+    its Gram is the line's roofline (the metric's "k-NN distance vs peak"),
+    and its per-stage device times (one more untimed pass);
   * config3_1gpu (N = 1): the metric's own 50k x 3M shape, bin-streamed;
+  * ingest_roofline (N = 1): the ingest's inflate launch against HBM;
   * cpu_baseline: the oracle on a bounded slice, and the committed sweep.
+
+``--dump-outputs DIR`` writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64; seeded samples of the large ones): from
+files, the output files parsed back into arrays; for the chain headline, the
+chain's device outputs.  Same arguments, same inputs, run after run.
 
 Multi-GPU: one rank per GPU over RCCL.  ``--gpus N`` without an external
 launcher starts ``torch.distributed.run`` with N ranks as a child process
 before anything touches the GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--headline files|chain]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--headline files|chain] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -47,6 +56,7 @@ TRAFFIC_JSON = "profiles/r05az_pmc_traffic.json"
 # run on a GPU box's host cores); reported beside the live bounded sample
 CPU_SWEEP_JSON = "profiles/r04k_cpu_sweep.json"
 GRAM_KERNEL = "k_gram8<0, true"
+DTYPE = "f64 (statistics) + bf16-MFMA exact-integer (k-NN)"
 SEED = 20260821
 NCL = 26
 M64 = (1 << 64) - 1
@@ -192,13 +202,14 @@ def cpu_baseline_from_files(n_target, m_target, k, n_iters):
 FILES_DIRNAME = "grid_bench_cfg2"
 
 
-def prepare_files_cohort(data, out, n, m, gen_threads=16, threads=16, bgzf=True, note=print):
+def prepare_files_cohort(data, out, n, m, gen_threads=16, threads=16, bgzf=True, note=print, meanwhile=None):
     """The from-files cohort in ``data``: ``n`` mosdepth regions.bed.gz files
     of ``m`` 1 kb bins (tools/gen_cohort: the bench's depth model as "%.2f"
-    text, BGZF like mosdepth, libdeflate level 1), samples.txt, an empty
+    text, BGZF like mosdepth, its own line-structured deflate encoder), samples.txt, an empty
     repeat mask, the IBS hap-neighbour file (synth_reads_and_ibs), counts.tsv
     in ``out`` and config.yaml (`grid wgs` steps 4-7, k = 10, n_iters = 100).
-    Runs before anything touches the GPU (a child process).  Returns
+    Runs before anything touches the GPU (a child process); the small files
+    are written, and ``meanwhile()`` called, while the generator runs.  Returns
     (config path, generation seconds, cohort bytes)."""
     import gzip
     import yaml
@@ -211,10 +222,11 @@ def prepare_files_cohort(data, out, n, m, gen_threads=16, threads=16, bgzf=True,
     if not os.path.exists(gen) or os.path.getmtime(gen) < os.path.getmtime(gen + ".cpp"):
         subprocess.run(["g++", "-O3", "-std=c++17", "-pthread", "-o", gen, gen + ".cpp", "-lz", "-ldl"], check=True)
     have = len([f for f in os.listdir(mos) if f.endswith(".regions.bed.gz")])
+    child = None
     if have != n:
         note(f"generating {n} x {m} mosdepth files in {mos}")
-        subprocess.run([gen, mos, str(n), str(m), "20260821", str(gen_threads), "0"] + (["bgzf"] if bgzf else []),
-                       check=True, stdout=sys.stderr)
+        cmd = [gen, mos, str(n), str(m), "20260821", str(gen_threads), "0"] + (["bgzf"] if bgzf else [])
+        child = subprocess.Popen(cmd, stdout=sys.stderr)
     ids = [f"S{i:05d}" for i in range(n)]
     reads, off, nbr, w = synth_reads_and_ibs(n)
     with open(os.path.join(data, "samples.txt"), "w") as f:
@@ -247,6 +259,10 @@ def prepare_files_cohort(data, out, n, m, gen_threads=16, threads=16, bgzf=True,
     path = os.path.join(data, "config.yaml")
     with open(path, "w") as f:
         yaml.safe_dump(cfg, f)
+    if meanwhile is not None:
+        meanwhile()
+    if child is not None and child.wait() != 0:
+        raise subprocess.CalledProcessError(child.returncode, cmd)
     nbytes = sum(os.path.getsize(os.path.join(mos, f)) for f in os.listdir(mos))
     return path, time.perf_counter() - t0, nbytes
 
@@ -283,8 +299,10 @@ def files_prepare(args, rank, local, world, note):
         else:
             note("from files: generating the BGZF cohort (outside the clock)")
             try:
+                # the generator is a child process: torch is imported (no device touched) while it runs
                 res = prepare_files_cohort(data, out, args.samples, args.bins, gen_threads=16,
-                                           threads=args.files_threads, note=note)
+                                           threads=args.files_threads, note=note,
+                                           meanwhile=lambda: __import__("torch"))
             except (OSError, subprocess.CalledProcessError) as e:
                 res = {"skipped": f"cohort generation: {e}"}
         if world > 1:
@@ -458,7 +476,7 @@ def files_leg(args, prep, steps, warmup, world, rank, dist, note):
     data, out = files_paths(args)
     outputs = {f: os.path.getsize(os.path.join(out, f)) for f in sorted(os.listdir(out))} if rank == 0 else None
     digests = None
-    if rank == 0:
+    if rank == 0 and args.full:              # a check of the outputs beside the headline
         try:
             import xxhash
             import gzip
@@ -506,6 +524,141 @@ def cpu_sweep_fit():
                                     "matrix does not fit host memory at configs 2-3"}
 
 
+DUMP_ROWS, DUMP_COLS = 4, 500_000
+
+
+def _save(dump_dir, name, a):
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def _floats(fields):
+    return np.array([np.nan if v in ("NA", "nan", "") else float(v) for v in fields], dtype=np.float64)
+
+
+def remove_trees(dirs, threads=16):
+    """The cohort and the outputs removed (tens of GB in --files-dir): the
+    files unlinked from ``threads`` threads, then what is left of the trees."""
+    import shutil
+    from concurrent.futures import ThreadPoolExecutor
+    paths = [os.path.join(r, f) for d in dirs for r, _, fs in os.walk(d) for f in fs]
+
+    def rm(p):
+        try:
+            os.unlink(p)
+        except OSError:
+            pass
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(rm, paths))
+    for d in dirs:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def dump_files_outputs(out_dir, ids, dump_dir):
+    """--dump-outputs, from-files headline: what the last run_wgs_pipeline
+    call wrote, parsed back into arrays (rows in samples.txt order, sample ids
+    as row indices, float64): the neighbour lists, dipCN, the haploid table,
+    and of the normalised matrix (GBs of text) the first DUMP_ROWS rows and
+    the two header rows at DUMP_COLS columns drawn with the bench's seed."""
+    import gzip
+    pos = {s: i for i, s in enumerate(ids)}
+    n = len(ids)
+    names = sorted(os.listdir(out_dir))
+
+    def find(prefix):
+        hit = [f for f in names if f.startswith(prefix + ".")]
+        if len(hit) != 1:
+            raise RuntimeError(f"--dump-outputs: {len(hit)} files {prefix}.* in {out_dir}")
+        return os.path.join(out_dir, hit[0])
+
+    # step 5: ID, scale, then (neighbour ID, its scale, distance) triples
+    with gzip.open(find("neighbors"), "rt") as f:
+        rows = [line.rstrip("\n").split("\t") for line in f]
+    k = max((len(p) - 2) // 3 for p in rows)
+    nb_scale = np.full(n, np.nan)
+    nb_idx, nb_sc, nb_d = (np.full((n, k), np.nan) for _ in range(3))
+    for p in rows:
+        i = pos[p[0]]
+        nb_scale[i] = float(p[1])
+        t = (len(p) - 2) // 3
+        nb_idx[i, :t] = [pos[s] for s in p[2:2 + 3 * t:3]]
+        nb_sc[i, :t] = _floats(p[3:2 + 3 * t:3])
+        nb_d[i, :t] = _floats(p[4:2 + 3 * t:3])
+    _save(dump_dir, "neighbors_scale", nb_scale)
+    _save(dump_dir, "neighbors_index", nb_idx)
+    _save(dump_dir, "neighbors_nbr_scale", nb_sc)
+    _save(dump_dir, "neighbors_distance", nb_d)
+    # step 6: Sample, Norm_Reads
+    dip = np.full(n, np.nan)
+    with open(find("dipcn")) as f:
+        next(f)
+        for line in f:
+            p = line.split()
+            if len(p) >= 2:
+                dip[pos[p[0]]] = float(p[1])
+    _save(dump_dir, "dipcn", dip)
+    # step 7: ID, IRRs, hap1phased, hap2phased, hap1imp, hap2imp
+    hap = np.full((n, 5), np.nan)
+    with open(find("haploid")) as f:
+        next(f)
+        for line in f:
+            p = line.rstrip("\n").split("\t")
+            if len(p) >= 6:
+                hap[pos[p[0]]] = _floats(p[1:6])
+    _save(dump_dir, "haploid", hap)
+    # step 4: "n r means...", "n r ratios...", then "ID raw z..." per sample
+    rng = np.random.default_rng(SEED)
+    with gzip.open(find("normalized"), "rt") as f:
+        head = [f.readline().rstrip("\n").split("\t") for _ in range(2)]
+        r = int(head[0][1])
+        cols = np.sort(rng.choice(r, size=min(r, DUMP_COLS), replace=False))
+        _save(dump_dir, "normalized_shape", np.array([float(head[0][0]), float(r)]))
+        _save(dump_dir, "normalized_columns", cols.astype(np.float64))
+        _save(dump_dir, "normalized_means", _floats([head[0][2 + j] for j in cols]))
+        _save(dump_dir, "normalized_ratios", _floats([head[1][2 + j] for j in cols]))
+        zrow = np.full(DUMP_ROWS, np.nan)
+        zraw = np.full(DUMP_ROWS, np.nan)
+        z = np.full((DUMP_ROWS, len(cols)), np.nan, dtype=np.float32)
+        for i in range(DUMP_ROWS):
+            p = f.readline().rstrip("\n").split("\t")
+            if len(p) < 2:
+                break
+            zrow[i], zraw[i] = pos[p[0]], float(p[1])
+            z[i] = _floats([p[2 + j] for j in cols])
+    _save(dump_dir, "normalized_rows", zrow)
+    _save(dump_dir, "normalized_row_means", zraw)
+    _save(dump_dir, "normalized_z", z)
+
+
+def dump_chain_outputs(st, n, dump_dir):
+    """--dump-outputs, chain headline: the device outputs of the last timed
+    pass (after finish()), float64: the row means, the column means and
+    variances at DUMP_COLS columns drawn with the bench's seed, the neighbour
+    indices, squared distances and counts, dipCN and its validity, the phased
+    and imputed haplotype values and their mean."""
+    def host(t):
+        return t.detach().cpu().numpy().astype(np.float64)
+    ml = int(st.mu.shape[0])
+    cols = np.sort(np.random.default_rng(SEED).choice(ml, size=min(ml, DUMP_COLS), replace=False))
+    _save(dump_dir, "row_means", host(st.rm[:n]))
+    _save(dump_dir, "columns", cols.astype(np.float64))
+    _save(dump_dir, "column_means", host(st.mu)[cols])
+    _save(dump_dir, "column_variances", host(st.var)[cols])
+    idx, d2, cnt = host(st.idx_out[:n]), host(st.d2[:n]), host(st.cnt_out[:n])
+    unused = np.arange(idx.shape[1])[None, :] >= cnt[:, None]      # slots past a row's count hold nothing
+    idx[unused] = np.nan
+    d2[unused] = np.nan
+    _save(dump_dir, "neighbors_index", idx)
+    _save(dump_dir, "neighbors_d2", d2)
+    _save(dump_dir, "neighbors_count", cnt)
+    valid = host(st.valid[:n])
+    _save(dump_dir, "dipcn", np.where(valid != 0, host(st.dip[:n]), np.nan))
+    _save(dump_dir, "dipcn_valid", valid)
+    _save(dump_dir, "haploid", host(st.hap[: 2 * n]))
+    _save(dump_dir, "haploid_imputed", host(st.imp[: 2 * n]))
+    _save(dump_dir, "haploid_mean", host(st.mean))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -548,9 +701,12 @@ def plan_memory(n, ml, world, budget, shard="bin", piece_bytes=0):
     return min(chunk, -(-ml // 8192) * 8192), fixed + per_col * chunk
 
 
-def run_workload(args, n, m, steps, warmup, world, rank, local, dist, comm, dev, note, profile_pass=True):
+def run_workload(args, n, m, steps, warmup, world, rank, local, dist, comm, dev, note, profile_pass=True,
+                 dump_dir=None):
     """One workload's timed steps (steps 4-7 of an n x m cohort over `world`
-    ranks): the bench line's fields for it.  With --sim-world W the process
+    ranks): the bench line's fields for it.  ``profile_pass``: one more
+    untimed pass for the per-stage device times (stages_ms).  ``dump_dir``:
+    rank 0 writes the last timed pass's outputs there.  With --sim-world W the process
     is rank --sim-rank of a simulated W-rank run on one GPU (fused.SimComm):
     `world` / `rank` are then the simulated ones, the clock this process's."""
     import torch
@@ -655,6 +811,8 @@ def run_workload(args, n, m, steps, warmup, world, rank, local, dist, comm, dev,
     elapsed = float(el.item())
     gms = sum(a.elapsed_time(b) for a, b in gram_pairs) / max(steps, 1)      # Gram ms per step
     glaunch = len(gram_pairs) // max(steps, 1)
+    if dump_dir and (rank == 0 or args.sim_world):
+        dump_chain_outputs(st, n, dump_dir)   # the last timed pass's, before any further pass
     stages = None
     if profile_pass:
         st.run(q, ldq, profile=True)          # untimed pass: per-stage device times
@@ -698,7 +856,7 @@ def run_workload(args, n, m, steps, warmup, world, rank, local, dist, comm, dev,
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
-        "dtype": "f64 (statistics) + bf16-MFMA exact-integer (k-NN)",
+        "dtype": DTYPE,
         "data": "synthetic (counter-based cohort generated in HBM; 26 ancestry clusters)",
         "config": {"workload": f"{cfgname}: {n} samples x {m} bins, k={args.k}, n_iters={args.n_iters}, "
                                f"{world} GPU(s){streamed_note}",
@@ -746,6 +904,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--samples", type=int, default=3202)
     ap.add_argument("--bins", type=int, default=3_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, from runs of their own: the device chain with its Gram roofline and "
+                         "per-stage times (when the headline is from files), the config-3 shape, the ingest roofline "
+                         "and the CPU baselines (the --cpu-*, --config3-*, --no-cpu-baseline and --files-baseline "
+                         "options apply here); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64; "
+                         "seeded samples of the large outputs)")
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--n-iters", type=int, default=100)
     ap.add_argument("--chunk", type=int, default=0, help="bins per streamed chunk (multiple of 8192); "
@@ -852,7 +1018,7 @@ def main():
         from grid_amd.fused import SimComm
         comm = SimComm(args.sim_world, args.sim_rank)
         out, timing = run_workload(args, n, m, args.steps, args.warmup, args.sim_world, args.sim_rank, local, None,
-                                   comm, dev, note)
+                                   comm, dev, note, profile_pass=args.full, dump_dir=args.dump_outputs)
         out["n_gpus"] = 1
         out["value"] = None          # not a job throughput: one rank's work of a W-rank step
         out["rank_ms_per_step"] = out["ms_per_step"]
@@ -869,17 +1035,34 @@ def main():
         else:
             note(f"from files: {n} x {m}, {world} rank(s); warmup {args.warmup}, steps {args.steps}")
             files = files_leg(args, prep, args.steps, args.warmup, world, rank, dist, note)
-        # the pipeline's device context holds its ingest buffers: free them for the chain below
-        from grid_amd.device import release_ingest_buffers
-        release_ingest_buffers()
-        torch.cuda.empty_cache()
+            if args.dump_outputs and rank == 0:
+                data_dir, out_dir = files_paths(args)
+                with open(os.path.join(data_dir, "samples.txt")) as f:
+                    dump_files_outputs(out_dir, f.read().split(), args.dump_outputs)
+    from_files = files is not None and "value" in files
+    # the device chain: the headline itself, or with --full beside the from-files headline
+    chain = None
+    if args.full or not from_files:
+        if headline == "files":
+            # the pipeline's device context holds its ingest buffers: free them for the chain below
+            from grid_amd.device import release_ingest_buffers
+            release_ingest_buffers()
+            torch.cuda.empty_cache()
 
-    # ---- the device chain (inputs generated in HBM): the Gram's roofline ----
-    dev = _abi.Device(local)
-    dev.set_stream(torch.cuda.current_stream())
-    chain, timing = run_workload(args, n, m, args.steps, args.warmup, world, rank, local, dist, comm, dev, note)
-    if files is not None and "value" in files:
-        out = dict(chain)
+        # ---- the device chain (inputs generated in HBM): the Gram's roofline ----
+        dev = _abi.Device(local)
+        dev.set_stream(torch.cuda.current_stream())
+        chain, timing = run_workload(args, n, m, args.steps, args.warmup, world, rank, local, dist, comm, dev, note,
+                                     profile_pass=args.full, dump_dir=None if from_files else args.dump_outputs)
+    if from_files:
+        if chain is None:
+            out = {"metric": METRIC, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                   "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": DTYPE,
+                   "stages_ms": None, "roofline": None,
+                   "not_measured": "device_chain, roofline, stages_ms, config3_1gpu, ingest_roofline and cpu_baseline "
+                                   "take runs of their own: --full"}
+        else:
+            out = dict(chain)
         out["value"] = files["value"]
         out["ms_per_step"] = files["ms_per_step"]
         out["data"] = ("synthetic mosdepth BGZF cohort on disk (tools/gen_cohort: the bench's 26-cluster depth model "
@@ -895,21 +1078,22 @@ def main():
             "threads": args.files_threads, "step": "one whole run_wgs_pipeline call (ingest buffers kept cached between "
                                                   "runs; outputs rewritten every run)"}
         out["from_files"] = files
-        dc = {k: chain[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "config", "stages_ms")}
-        dc["data"] = chain["data"]
-        dc["roofline"] = chain["roofline"]
-        out["device_chain"] = dc
-        out["roofline"] = dict(chain["roofline"], measured_in="device_chain (the same config-2 shape, inputs in HBM; "
-                                                              "the metric's k-NN distance kernel)")
+        if chain is not None:
+            dc = {k: chain[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "config", "stages_ms")}
+            dc["data"] = chain["data"]
+            dc["roofline"] = chain["roofline"]
+            out["device_chain"] = dc
+            out["roofline"] = dict(chain["roofline"], measured_in="device_chain (the same config-2 shape, inputs in "
+                                                                  "HBM; the metric's k-NN distance kernel)")
     else:
         out = chain
         if files is not None:
             out["from_files"] = files
     # the metric's own shape (BASELINE config 3: 50k x 3M, streamed on one
     # GPU): one more timed measurement in the same run, beside the line's
-    # workload (N = 1 only: the scaling runs keep one workload per N)
+    # workload (N = 1 only: the scaling runs keep one workload per N; --full)
     c3 = None
-    if world == 1 and args.config3_steps > 0 and (n, m) != (50_000, 3_000_000):
+    if args.full and world == 1 and args.config3_steps > 0 and (n, m) != (50_000, 3_000_000):
         note("config 3 shape (50,000 x 3,000,000, streamed) as a second measurement")
         o3, _ = run_workload(args, 50_000, 3_000_000, args.config3_steps, args.config3_warmup, world, rank, local, dist,
                              comm, dev, note, profile_pass=False)
@@ -919,13 +1103,13 @@ def main():
         c3["gram_frac_2N2R"] = o3["roofline"]["frac"]
         c3["executed_frac"] = o3["roofline"]["executed_frac"]
         out["config3_1gpu"] = c3
-    if rank == 0 and world == 1 and headline == "files" and files is not None and "value" in files:
+    if args.full and rank == 0 and world == 1 and from_files:
         try:
             out["ingest_roofline"] = inflate_roofline(files_paths(args)[0], dev, note)
         except Exception as e:                     # the line still prints; the reason is on it
             out["ingest_roofline"] = {"error": repr(e)[:300]}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         c0 = 0
         ns, ms = min(args.cpu_samples, n), min(args.cpu_bins, m)
         qs = torch.empty((ns, ms), dtype=torch.int32, device="cuda")   # same cells, int32 form
@@ -977,12 +1161,12 @@ def main():
     if rank == 0:
         out["build"] = _abi.build_info()          # the library's source sha256 = this tree's (checked at load)
         print(json.dumps(out), file=result_out, flush=True)
+        note("result line printed")
     if dist:
         dist.barrier()
     if headline == "files" and rank == 0 and not args.keep_files:
-        import shutil
-        for d in files_paths(args):
-            shutil.rmtree(d, ignore_errors=True)
+        remove_trees(files_paths(args))
+        note("cohort and outputs removed")
     if dist:
         dist.destroy_process_group()
 
