@@ -169,6 +169,15 @@ _SIGS = {
     "grid_gz_parts_size": [_vp, C.POINTER(_i64)],
     "grid_gz_parts_write": [_vp, C.c_char_p, _i64, _i32],
     "grid_gz_parts_free": [_vp],
+    # step 5's read on the device (grid_amd/utils/ntext_device.py)
+    "grid_ntext_count": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "grid_ntext_parse": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
+    "grid_ntext_prefix": [_vp, _vp, _i64, _vp, _i64, _vp],
+    "grid_ntext_parse_host": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, C.POINTER(_i32), C.POINTER(_i64)],
+    "grid_ntext_rows_host": [_vp, _i64, _vp, _i64, C.POINTER(_i64), _vp, _vp],
+    "grid_ntext_index_open": [C.c_char_p, _i32, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+    "grid_ntext_index_fetch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "grid_ntext_index_free": [_vp],
 }
 EXPORTS = tuple(_SIGS) + ("grid_last_error", "grid_build_info")
 
@@ -228,8 +237,8 @@ def load():
 # the files grid_amd/csrc/Makefile hashes into the library (HASHED), in its sorted order
 _CSRC = _HERE / "csrc"
 _HASHED = sorted(["core.hip", "normalize.hip", "knn.hip", "dipcn_phase.hip", "synth.hip", "depth16.hip",
-                  "inflate.hip", "mosdepth_dev.hip", "gzwrite.hip", "ingest.cpp", "textio.cpp", "hapnbr.cpp",
-                  "common.hpp", "synth_model.hpp", "inflate_core.hpp", "fastgz.hpp"])
+                  "inflate.hip", "mosdepth_dev.hip", "gzwrite.hip", "ntext_dev.hip", "ingest.cpp", "textio.cpp",
+                  "hapnbr.cpp", "common.hpp", "synth_model.hpp", "inflate_core.hpp", "ntext_core.hpp", "fastgz.hpp"])
 
 
 def source_sha256(names=None):
@@ -619,6 +628,76 @@ def read_normalized_gz(path, threads=None):
         return ids, scales, means, ratios, zq
     finally:
         lib.grid_ntext_free(h)
+
+
+NT_BADCELL, NT_BADROW, NT_LEADWS, NT_CR, NT_NOEOL, NT_ROWRANGE, NT_PREFIX, NT_BADSCALE = (1 << k for k in range(8))
+NT_PREFIX_BYTES = 512
+NT_FLAG_NAMES = {NT_BADCELL: "a cell outside the %.2f grammar", NT_BADROW: "a row whose length differs from R",
+                 NT_LEADWS: "a row starting with a space or a tab", NT_CR: "a carriage return",
+                 NT_NOEOL: "a member that does not end in a newline", NT_ROWRANGE: "a row outside [0, N)",
+                 NT_PREFIX: "a row whose second tab lies beyond its first 512 bytes", NT_BADSCALE: "a bad scale"}
+
+
+def ntext_flag_text(flags) -> str:
+    return "; ".join(t for b, t in NT_FLAG_NAMES.items() if int(flags) & b) or f"flags {int(flags)}"
+
+
+def ntext_index(path, header=True):
+    """Member table and header member of an indexed normalised file
+    (grid_ntext_index_*): dict(n, r, off, len, first_row, isize, means,
+    ratios), the arrays over the row members in file order; header=False: the
+    member table only (n = r = -1, no means or ratios).  Raises
+    GridNativeError(code GRID_EUNSUPPORTED) for a file without the index."""
+    lib = load()
+    h, m, n, r = _vp(), _i64(), _i64(), _i64()
+    check(lib.grid_ntext_index_open(str(path).encode(), 1 if header else 0, C.byref(h), C.byref(m), C.byref(n),
+                                    C.byref(r)), "grid_ntext_index_open")
+    try:
+        m, n, r = m.value, max(n.value, 0), max(r.value, 0)
+        a = [np.zeros(max(m, 1), np.int64) for _ in range(4)]
+        means, ratios = np.empty(max(r, 1)), np.empty(max(r, 1))
+        call("grid_ntext_index_fetch", h, *(x.ctypes.data for x in a), means.ctypes.data, ratios.ctypes.data)
+        return {"n": n if header else -1, "r": r if header else -1, "off": a[0][:m], "len": a[1][:m], "first_row": a[2][:m], "isize": a[3][:m],
+                "means": means[:r], "ratios": ratios[:r]}
+    finally:
+        lib.grid_ntext_index_free(h)
+
+
+def ntext_parse_host(text, first_row, n, r, zq, rowoff, tbase=0):
+    """The device parser's count / scan / parse run serially on the host over
+    one member's text (grid_ntext_parse_host) into zq [n][ld] int32 and
+    rowoff [n] int64; returns (flag bits, newlines)."""
+    a = np.frombuffer(text, np.uint8) if not isinstance(text, np.ndarray) else text
+    assert zq.dtype == np.int32 and zq.flags.c_contiguous and rowoff.dtype == np.int64
+    fl, nr = _i32(), _i64()
+    call("grid_ntext_parse_host", a.ctypes.data if a.size else None, a.size, int(first_row), int(n), int(r),
+         zq.ctypes.data, zq.shape[1], rowoff.ctypes.data, int(tbase), C.byref(fl), C.byref(nr))
+    return fl.value, nr.value
+
+
+def ntext_rows(prefix):
+    """IDs and scales of row prefixes [rows][NT_PREFIX_BYTES] uint8
+    (grid_ntext_rows_host: the host reader's parse_float): (ids, scales,
+    flags [rows])."""
+    prefix = np.ascontiguousarray(prefix, np.uint8).reshape(-1, NT_PREFIX_BYTES)
+    n = len(prefix)
+    cap = n * (NT_PREFIX_BYTES + 1) + 1
+    buf = C.create_string_buffer(cap)
+    ln = _i64()
+    scales, flags = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
+    call("grid_ntext_rows_host", prefix.ctypes.data if n else None, n, buf, cap, C.byref(ln), scales.ctypes.data,
+         flags.ctypes.data)
+    ids = buf.raw[: ln.value].decode().split("\n")[:n]
+    return ids, scales[:n], flags[:n]
+
+
+def read_normalized_gz_dev(dev, path, threads=None, timings=None):
+    """read_normalized_gz with the row members inflated and parsed on the
+    device: (ids, scales [n], means [r], ratios [r], zq DevBuf [n][r] int32),
+    every value what read_normalized_gz returns -- or raises
+    utils.ntext_device.DeviceReadUnsupported and the caller uses that reader."""
+    from .utils import ntext_device
+    return ntext_device.read(dev, path, threads=threads, timings=timings)
 
 
 def _hapnbr_result(rc, h, nnz, n, what):

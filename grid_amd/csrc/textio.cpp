@@ -860,4 +860,116 @@ int grid_ntext_free(void *h) {
   return GRID_OK;
 }
 
+// ---- the device reader's host side (ntext_dev.hip, utils/ntext_device.py) ----
+struct NIndex {
+  std::vector<Member> ms;            // row members (member 0 excluded)
+  std::vector<int64_t> isize;
+  int64_t n = 0, r = 0;
+  std::vector<double> means, ratios;
+};
+
+int grid_ntext_index_open(const char *path, int32_t header, void **h_out, int64_t *nmembers, int64_t *n,
+                          int64_t *r) {
+  if (!path || !h_out || !nmembers || !n || !r) {
+    grid_set_error("grid_ntext_index_open: bad args");
+    return GRID_EINVAL;
+  }
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) {
+    grid_set_error("cannot open %s", path);
+    return GRID_EINVAL;
+  }
+  struct stat stt;
+  const size_t size = fstat(fd, &stt) == 0 ? (size_t)stt.st_size : 0;
+  void *map = size ? mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0) : MAP_FAILED;
+  close(fd);
+  if (map == MAP_FAILED) {
+    grid_set_error("%s: empty or unreadable", path);
+    return GRID_EUNSUPPORTED;
+  }
+  const unsigned char *b = (const unsigned char *)map;
+  std::vector<Member> ms = index_members(b, size);
+  auto t = std::unique_ptr<NIndex>(new NIndex());
+  std::string head;
+  int64_t n1 = 0, r1 = 0;
+  bool ok = !ms.empty() && ms[0].first_row == -1;
+  t->n = t->r = -1;
+  if (ok && header) {
+    ok = inflate_member(b + ms[0].off, ms[0].len, head);
+    const size_t nl0 = ok ? head.find('\n') : std::string::npos;
+    const size_t nl1 = nl0 != std::string::npos ? head.find('\n', nl0 + 1) : std::string::npos;
+    ok = ok && nl1 != std::string::npos && nl1 + 1 == head.size() &&
+         parse_header_line(head.substr(0, nl0), t->n, t->r, t->means) &&
+         parse_header_line(head.substr(nl0 + 1, nl1 - nl0 - 1), n1, r1, t->ratios) && n1 == t->n && r1 == t->r;
+  }
+  if (ok) {
+    t->ms.assign(ms.begin() + 1, ms.end());
+    for (const auto &m : t->ms) t->isize.push_back((int64_t)get_le(b + m.off + m.len - 4, 4));
+  }
+  munmap(map, size);
+  if (!ok) {
+    grid_set_error("%s: no 'GR' member index with a header member", path);
+    return GRID_EUNSUPPORTED;
+  }
+  *nmembers = (int64_t)t->ms.size();
+  *n = t->n;
+  *r = t->r;
+  *h_out = t.release();
+  return GRID_OK;
+}
+
+int grid_ntext_index_fetch(const void *h, int64_t *off, int64_t *len, int64_t *first_row, int64_t *isize,
+                           double *means, double *ratios) {
+  if (!h) { grid_set_error("bad args"); return GRID_EINVAL; }
+  const NIndex *t = (const NIndex *)h;
+  for (size_t k = 0; k < t->ms.size(); k++) {
+    if (off) off[k] = (int64_t)t->ms[k].off;
+    if (len) len[k] = (int64_t)t->ms[k].len;
+    if (first_row) first_row[k] = t->ms[k].first_row;
+    if (isize) isize[k] = t->isize[k];
+  }
+  if (means) memcpy(means, t->means.data(), t->means.size() * sizeof(double));
+  if (ratios) memcpy(ratios, t->ratios.data(), t->ratios.size() * sizeof(double));
+  return GRID_OK;
+}
+
+int grid_ntext_index_free(void *h) {
+  delete (NIndex *)h;
+  return GRID_OK;
+}
+
+int grid_ntext_rows_host(const uint8_t *h_prefix, int64_t nrows, char *h_ids_nl, int64_t ids_cap, int64_t *ids_len,
+                         double *h_scales, int32_t *h_flags) {
+  if (nrows < 0 || !ids_len || (nrows && (!h_prefix || !h_ids_nl || !h_scales || !h_flags))) {
+    grid_set_error("grid_ntext_rows_host: bad args");
+    return GRID_EINVAL;
+  }
+  int64_t pos = 0;
+  for (int64_t i = 0; i < nrows; i++) {
+    const char *p = (const char *)h_prefix + i * GRID_NT_PREFIX_BYTES;
+    const char *nl = (const char *)memchr(p, '\n', GRID_NT_PREFIX_BYTES);
+    const char *e = nl ? nl : p + GRID_NT_PREFIX_BYTES;
+    const char *t1 = (const char *)memchr(p, '\t', (size_t)(e - p));
+    const char *t2 = t1 ? (const char *)memchr(t1 + 1, '\t', (size_t)(e - t1 - 1)) : nullptr;
+    h_flags[i] = 0;
+    h_scales[i] = 0.0;
+    if (!t2) {                       // the row ends first (no cell), or the prefix does
+      h_flags[i] = nl ? GRID_NT_BADROW : GRID_NT_PREFIX;
+      if (pos + 1 > ids_cap) { grid_set_error("ids buffer too small"); return GRID_ERANGE; }
+      h_ids_nl[pos++] = '\n';
+      continue;
+    }
+    bool ok = true;
+    h_scales[i] = parse_float(t1 + 1, t2, ok);
+    if (!ok) h_flags[i] = GRID_NT_BADSCALE;
+    const int64_t k = t1 - p;
+    if (pos + k + 1 > ids_cap) { grid_set_error("ids buffer too small"); return GRID_ERANGE; }
+    memcpy(h_ids_nl + pos, p, (size_t)k);
+    pos += k;
+    h_ids_nl[pos++] = '\n';
+  }
+  *ids_len = pos;
+  return GRID_OK;
+}
+
 }  // extern "C"

@@ -16,6 +16,7 @@ distances differ (sklearn's own tie order is undefined).
 from __future__ import annotations
 
 import gzip
+import os
 from pathlib import Path
 
 import numpy as np
@@ -61,6 +62,31 @@ def _read_normalized_q(input_file):
         if e.code != _abi.GRID_EUNSUPPORTED:
             raise
     return _read_normalized_q_py(input_file)
+
+
+def _read_normalized_dev(config, console, input_file):
+    """The device reader (utils/ntext_device.py) when the config asks for it
+    (mosdepth.neighbors.device_read: true) or, with the key absent, when its
+    cost rule prefers it: (ids, {id: scale}, zq DevBuf [n][r], ratios), or
+    None -- the key is false, the rule prefers the host reader, or the reader
+    handed over (one warning line names the reason)."""
+    from .. import device
+    from . import ntext_device
+    want = config["mosdepth"]["neighbors"].get("device_read")
+    if want is not None and not want:
+        return None
+    dev = get_device(config)
+    threads = min(16, os.cpu_count() or 1)      # what _abi.read_normalized_gz runs with
+    if want is None and not ntext_device.auto_choice(dev, input_file, threads):
+        return None
+    try:
+        ids, sc, _means, ratios, zq = _abi.read_normalized_gz_dev(dev, input_file, threads=threads)
+    except ntext_device.DeviceReadUnsupported as e:
+        log(console, f"Warning: device read of {input_file} handed over to the host reader: {e}", style="warning")
+        return None
+    finally:
+        device.step4_done(dev)                  # the batch buffers go as step 4's do
+    return ids, {i: float(v) for i, v in zip(ids, sc)}, zq, ratios
 
 
 def _read_normalized_q_py(input_file):
@@ -174,7 +200,11 @@ def _find_neighbors_one(config, console, input_file, output_file, zmax, sigma2_m
         ids, sc, ratios, zq, _shape = got
         scales = {i: float(v) for i, v in zip(ids, sc)}
     else:
-        ids, scales, zq, ratios = _read_normalized_q(input_file)
+        got = _read_normalized_dev(config, console, input_file)
+        if got is not None:
+            ids, scales, zq, ratios = got
+        else:
+            ids, scales, zq, ratios = _read_normalized_q(input_file)
     N = len(ids)
     valid, R_use = filter_regions_by_variance(ratios, frac_r=frac_r, sigma2_max=sigma2_max, console=console)
 

@@ -730,6 +730,60 @@ int grid_gunzip_batch(grid_ctx *ctx, const uint8_t *d_src, const int64_t *d_in_o
                       grid_gz_member *d_mem, int32_t mcap, int32_t *d_status, int64_t *d_out_len,
                       int32_t *d_nmem);
 
+/* ---- normalised-matrix text -> int32 hundredths on the device (step 5's read;
+ * grid_amd/csrc/ntext_dev.hip, driven by grid_amd/utils/ntext_device.py).  A
+ * batch is the inflated text of several row members of a grid_write_normalized_gz
+ * file laid end to end: member m at d_text + d_toff[m] (256-B aligned), d_tlen[m]
+ * bytes, whole rows "ID \t scale \t z_1 ... z_R \n" from row d_first_row[m]; cut
+ * in 16 KiB chunks as the mosdepth text above (d_cfile / d_cstart / d_cfirst).
+ * Text outside the writer's grammar sets a flag of its member and never a value
+ * the host reader would not give; the caller then uses grid_read_normalized_gz. */
+#define GRID_NT_BADCELL 1    /* a cell outside -?D{1,8}.DD (<= 2147483647) / NA / nan */
+#define GRID_NT_BADROW 2     /* a newline where a tab belongs or the reverse (row length != R) */
+#define GRID_NT_LEADWS 4     /* a row starting with a space or a tab */
+#define GRID_NT_CR 8         /* a carriage return */
+#define GRID_NT_NOEOL 16     /* the member does not end in a newline */
+#define GRID_NT_ROWRANGE 32  /* a row outside [0, N) */
+#define GRID_NT_PREFIX 64    /* a row's second tab is not within its first GRID_NT_PREFIX_BYTES */
+#define GRID_NT_BADSCALE 128 /* a scale the host reader's parse_float refuses */
+#define GRID_NT_PREFIX_BYTES 512
+/* separators (tab, newline) and newlines per chunk; per member the field ordinal at each
+ * chunk start (d_cfield0) and its rows (d_nrows); d_flags |= GRID_NT_CR.  d_mstatus (may be
+ * NULL): members with a nonzero inflate status are skipped here and in grid_ntext_parse. */
+int grid_ntext_count(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                     int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart, const int32_t *d_cfirst,
+                     int64_t nmembers, int32_t *d_csep, int32_t *d_cnl, int64_t *d_cfield0, int64_t *d_nrows,
+                     int32_t *d_flags, const int32_t *d_mstatus);
+/* every cell -> d_zq[row * ld + column]; d_rowoff[row] = byte offset in d_text of the row */
+int grid_ntext_parse(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                     const int64_t *d_first_row, int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart,
+                     const int64_t *d_cfield0, int64_t n, int64_t r, int32_t *d_zq, int64_t ld, int64_t *d_rowoff,
+                     int32_t *d_flags, const int32_t *d_mstatus);
+/* d_prefix[row][GRID_NT_PREFIX_BYTES] = the row's first bytes (zeros past d_text + text_bytes)
+ * for every row with d_rowoff[row] >= 0, which is then reset to -1 (the caller starts from
+ * all -1) */
+int grid_ntext_prefix(grid_ctx *ctx, const uint8_t *d_text, int64_t text_bytes, int64_t *d_rowoff, int64_t n,
+                      uint8_t *d_prefix);
+/* host: the same count / scan / parse, serially, over one member's text in host memory
+ * (h_rowoff[row] = tbase + the row's offset); *flags, *nrows (newlines) */
+int grid_ntext_parse_host(const uint8_t *h_text, int64_t len, int64_t first_row, int64_t n, int64_t r, int32_t *h_zq,
+                          int64_t ld, int64_t *h_rowoff, int64_t tbase, int32_t *flags, int64_t *nrows);
+/* host: IDs ('\n'-joined into h_ids_nl, *ids_len bytes) and scales of nrows row prefixes
+ * (grid_ntext_prefix's), the scale by the host reader's own parse_float; h_flags[row] gets
+ * GRID_NT_PREFIX / GRID_NT_BADROW / GRID_NT_BADSCALE */
+int grid_ntext_rows_host(const uint8_t *h_prefix, int64_t nrows, char *h_ids_nl, int64_t ids_cap, int64_t *ids_len,
+                         double *h_scales, int32_t *h_flags);
+/* host: the member table of an indexed file and its parsed header member (N, R, means,
+ * ratios).  GRID_EUNSUPPORTED when the file has no 'GR' index throughout or member 0 is not
+ * the two header lines.  *nmembers counts the row members (member 0 excluded); _fetch gives
+ * their file offset, length, first row and ISIZE (any pointer may be NULL).  header == 0: the
+ * member table only -- member 0 is not inflated, *n = *r = -1, no means or ratios. */
+int grid_ntext_index_open(const char *path, int32_t header, void **h_out, int64_t *nmembers, int64_t *n,
+                          int64_t *r);
+int grid_ntext_index_fetch(const void *h, int64_t *off, int64_t *len, int64_t *first_row, int64_t *isize,
+                           double *means, double *ratios);
+int grid_ntext_index_free(void *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,7 +135,8 @@ timed(nm, "ingest", "step4_ingest")
 timed(nm, "_write_normalized_q", "step4_write_text")
 timed(engine, "normalize_stats", "step4_device_stats")
 timed(engine, "zquant", "step4_device_zquant")
-timed(fn, "_read_normalized_q", "step5_read_text")
+timed(fn, "_read_normalized_q", "step5_read_text")          # the host reader
+timed(fn, "_read_normalized_dev", "step5_read_text_device")  # the device reader (or its choice against it)
 timed(engine, "knn_from_zq", "step5_knn")
 timed(fn, "save_neighbors", "step5_write")
 
