@@ -1367,10 +1367,8 @@ __global__ void k_diag(const int64_t *__restrict__ g, int64_t np_, int64_t n, in
 
 // Neighbour keys: (d2 << 20) | j, unique per row, ordered by (d2, j); j < 2^20.
 // GramKey: exact integer d2 = G_ii + G_jj - 2 G_ij from full Gram rows
-// (the MFMA path).  D2Key: rows of precomputed d2 (the direct-difference path),
-// keyed on floor(d2 * scale) -- exact integers when scale = 1 and d2 < 2^44
-// (integer hundredths), a 44-bit fixed-point prefix of fp64 distances
-// otherwise -- with the emitted distance re-read from the row.
+// (the MFMA path).  Rows of precomputed fp64 d2 (the direct-difference path)
+// do not fit such a key: k_topk_d2 below orders them by (all 64 bits, j).
 struct GramKey {
   const int64_t *row;
   const int64_t *nrm;
@@ -1389,30 +1387,10 @@ struct GramKey {
   }
   __device__ __forceinline__ int64_t value(unsigned long long key) const { return (int64_t)(key >> 20); }
 };
-struct D2Key {
-  const double *row;
-  double scale;
-  typedef double out_t;
-  __device__ __forceinline__ unsigned long long key(int64_t j) const {
-    return ((unsigned long long)(row[j] * scale) << 20) | (unsigned long long)j;
-  }
-  __device__ __forceinline__ void load4(int64_t j, int64_t st, unsigned long long (&kk)[4]) const {
-    double v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) v[u] = row[j + u * st];
-#pragma unroll
-    for (int u = 0; u < 4; u++) kk[u] = ((unsigned long long)(v[u] * scale) << 20) | (unsigned long long)(j + u * st);
-  }
-  __device__ __forceinline__ double value(unsigned long long key) const { return row[key & 0xFFFFFull]; }
-};
 
 __device__ __forceinline__ GramKey make_src(const int64_t *rows, int64_t ld, const int64_t *nrm, double,
                                             int64_t orow, int64_t i) {
   return GramKey{rows + orow * ld, nrm, nrm[i]};
-}
-__device__ __forceinline__ D2Key make_src(const double *rows, int64_t ld, const int64_t *, double scale,
-                                          int64_t orow, int64_t) {
-  return D2Key{rows + orow * ld, scale};
 }
 
 // Write the ktake smallest keys of row i (ascending in s[0..ktake)) with self
@@ -1792,6 +1770,127 @@ __global__ __launch_bounds__(256) void k_topk_radix(const T *__restrict__ rows, 
     }
   }
   if (tid == 0) topk_emit(src, sel, ktake, i, k, orow, idx, (typename decltype(src)::out_t *)d2o, cnto);
+}
+
+// Row top-(k+1) of precomputed fp64 distances, ordered EXACTLY by (d2, j): a
+// non-negative double orders as its bit pattern, so the selection is a radix
+// select over the 64 value bits (8 passes; -0.0 counts as +0.0), then, only
+// when the (k+1)-th smallest value is shared by entries on both sides of the
+// boundary, over the 24 index bits of the entries with that value (3 passes);
+// the survivors -- exactly ktake -- are sorted as (bits, j) pairs.  No key is
+// shortened, so distances that differ in their last bit are told apart
+// whatever the largest distance of the matrix is.
+__global__ __launch_bounds__(256) void k_topk_d2(const double *__restrict__ rows, int64_t ld, int64_t n, int64_t k,
+                                                 int64_t row0, int32_t *__restrict__ idx, double *__restrict__ d2o,
+                                                 int32_t *__restrict__ cnto) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned long long s_prefix;
+  __shared__ long long s_rank;
+  __shared__ unsigned s_cnt;
+  __shared__ int s_nsel;
+  __shared__ unsigned long long sel_v[SELCAP];
+  __shared__ int32_t sel_j[SELCAP];
+  const int64_t orow = blockIdx.x, i = row0 + orow;
+  const double *row = rows + orow * ld;
+  const int tid = threadIdx.x;
+  const int64_t ktake = (k + 1 < n) ? k + 1 : n;
+  auto bits = [&](int64_t j) { return (unsigned long long)__double_as_longlong(row[j] + 0.0); };
+  // digit d of the bucket holding rank `rank`; the rank inside it
+  auto pick = [&](unsigned long long prefix, long long rank, int shift) {
+    long long cum = 0;
+    for (int d = 0; d < 256; d++) {
+      if (cum + hist[d] > rank) {
+        s_prefix = prefix | ((unsigned long long)d << shift);
+        s_rank = rank - cum;
+        s_cnt = hist[d];
+        break;
+      }
+      cum += hist[d];
+    }
+  };
+  unsigned long long prefix = 0, mask = 0;
+  long long rank = ktake - 1;
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    for (int64_t j = tid; j < n; j += 256) {
+      const unsigned long long b = bits(j);
+      if ((b & mask) == prefix) atomicAdd(&hist[(b >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) pick(prefix, rank, shift);
+    __syncthreads();
+    prefix = s_prefix;
+    rank = s_rank;
+    mask |= 0xFFull << shift;
+    __syncthreads();
+  }
+  const unsigned long long V = prefix;    // the ktake-th smallest value; rank + 1 of its s_cnt entries are taken
+  unsigned long long J = 0xFFFFFFull;     // ... those with j <= J
+  if ((long long)s_cnt != rank + 1) {
+    unsigned long long jp = 0, jm = 0;
+    for (int shift = 16; shift >= 0; shift -= 8) {
+      __syncthreads();
+      hist[tid] = 0;
+      __syncthreads();
+      for (int64_t j = tid; j < n; j += 256)
+        if (bits(j) == V && ((unsigned long long)j & jm) == jp) atomicAdd(&hist[(j >> shift) & 255], 1u);
+      __syncthreads();
+      if (tid == 0) pick(jp, rank, shift);
+      __syncthreads();
+      jp = s_prefix;
+      rank = s_rank;
+      jm |= 0xFFull << shift;
+    }
+    J = jp;
+  }
+  __syncthreads();
+  if (tid == 0) s_nsel = 0;
+  for (int e = tid; e < SELCAP; e += 256) { sel_v[e] = ~0ull; sel_j[e] = 0x7FFFFFFF; }
+  __syncthreads();
+  for (int64_t j = tid; j < n; j += 256) {
+    const unsigned long long b = bits(j);
+    if (b < V || (b == V && (unsigned long long)j <= J)) {
+      const int p = atomicAdd(&s_nsel, 1);
+      if (p < SELCAP) { sel_v[p] = b; sel_j[p] = (int32_t)j; }
+    }
+  }
+  __syncthreads();
+  int cap = 1;
+  while (cap < ktake) cap <<= 1;
+  for (int size = 2; size <= cap; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int e = tid; e < cap; e += 256) {
+        const int p = e ^ stride;
+        if (p > e) {
+          const bool up = (e & size) == 0;
+          const unsigned long long a = sel_v[e], b = sel_v[p];
+          const int32_t ja = sel_j[e], jb = sel_j[p];
+          const bool gt = a > b || (a == b && ja > jb);
+          if (gt == up) { sel_v[e] = b; sel_v[p] = a; sel_j[e] = jb; sel_j[p] = ja; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {                          // topk_emit's rule on the (bits, j) pairs
+    int64_t w = 0;
+    bool self = false;
+    for (int64_t e = 0; e < ktake; e++) {
+      const int64_t j = sel_j[e];
+      if (j == i && !self) { self = true; continue; }
+      if (w < k) {
+        idx[orow * k + w] = (int32_t)j;
+        d2o[orow * k + w] = __longlong_as_double((long long)sel_v[e]);
+        w++;
+      }
+    }
+    for (int64_t e = w; e < k; e++) {
+      idx[orow * k + e] = -1;
+      d2o[orow * k + e] = 0;
+    }
+    cnto[orow] = (int32_t)w;
+  }
 }
 
 // ---- general-value k-NN (values that are not bf16-exact) -----------------
@@ -2257,12 +2356,8 @@ int grid_knn_topk_d2(grid_ctx *ctx, const double *d_d2rows, int64_t ld, double k
     if (nrows) HIPCHK(hipMemsetAsync(d_cnt, 0, nrows * 4, ctx->stream));
     return GRID_OK;
   }
-  const int64_t ktake = k + 1 < n ? k + 1 : n;
-  auto kern = ktake <= 16 ? k_topk_small<16, double> : ktake <= 32 ? k_topk_small<32, double>
-                                                                     : k_topk_radix<double>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, d_d2rows, ld,
-                     (const int64_t *)nullptr, key_scale, n, k, row0, d_idx, (void *)d_d2, d_cnt, (int64_t)0,
-                     (unsigned long long *)nullptr);
+  hipLaunchKernelGGL(k_topk_d2, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, d_d2rows, ld, n, k, row0, d_idx,
+                     d_d2, d_cnt);
   LAUNCHCHK();
   return GRID_OK;
 }

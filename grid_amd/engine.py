@@ -186,15 +186,6 @@ def knn_from_hundredths(dev: Device, zq: np.ndarray, k: int, qmax: int):
     return _knn_zq(dev, zq, np.arange(zq.shape[1], dtype=np.int32), k, qmax / 100.0, False)
 
 
-def _dist_key_scale(bound: float, integer: bool) -> float:
-    """Power-of-two key scale with floor(d2 * scale) < 2^44 for d2 <= bound:
-    1 for exact integer distances that fit (they then stay exact), else the
-    finest scale (fp64 distances keep 44 significant bits of the largest)."""
-    if integer and bound < 2.0 ** 44:
-        return 1.0
-    return math.ldexp(1.0, 43 - math.frexp(bound)[1])
-
-
 def _knn_zq(dev: Device, zq: np.ndarray, cols: np.ndarray, k: int, zmax: float, values: bool):
     """Step 5 on integer hundredths zq [n][ld] (GRID_MISSING = NaN; GRID_ZQ_NEG0,
     the step-4 "-0.00" code in a hand-off, = 0) restricted
@@ -235,18 +226,16 @@ def _knn_zq(dev: Device, zq: np.ndarray, cols: np.ndarray, k: int, zmax: float, 
         call("grid_knn_gather_i32", dev.ctx, dz.ptr, n, ld, dcols.ptr, r, q, g.ptr)
         del dz, zq
         call("grid_knn_dist_i32", dev.ctx, g.ptr, n, r, max(r, 1), d2m.ptr, np_)
-        scale = _dist_key_scale(4.0 * q * q * max(r, 1), True)
         unit = 10000.0
     else:
         g = dev.alloc((n, max(r, 1)), F8)
         call("grid_knn_gather_f64", dev.ctx, dz.ptr, n, ld, dcols.ptr, r, float(zmax), g.ptr)
         del dz, zq
         call("grid_knn_dist_f64", dev.ctx, g.ptr, n, r, max(r, 1), d2m.ptr, np_)
-        scale = _dist_key_scale(4.0 * zmax * zmax * max(r, 1) + 1.0, False)
         unit = 1.0
     del g
     idx, d2, cnt = dev.alloc((n, kk), I4), dev.alloc((n, kk), F8), dev.alloc(n, I4)
-    call("grid_knn_topk_d2", dev.ctx, d2m.ptr, np_, scale, n, k, 0, n, idx.ptr, d2.ptr, cnt.ptr)
+    call("grid_knn_topk_d2", dev.ctx, d2m.ptr, np_, 1.0, n, k, 0, n, idx.ptr, d2.ptr, cnt.ptr)
     d2h = d2.numpy()
     if values:
         return idx.numpy(), d2h / unit, cnt.numpy()
@@ -283,10 +272,8 @@ def knn_values(dev: Device, data: np.ndarray, k: int):
     dz = dev.upload(data)
     d2m = dev.alloc((np_, np_), F8)
     call("grid_knn_dist_f64", dev.ctx, dz.ptr, n, r, r, d2m.ptr, np_)
-    m = float(np.abs(data).max()) if data.size else 0.0
-    scale = _dist_key_scale(4.0 * m * m * max(r, 1) + 1.0, False)
     idx, d2, cnt = dev.alloc((n, kk), I4), dev.alloc((n, kk), F8), dev.alloc(n, I4)
-    call("grid_knn_topk_d2", dev.ctx, d2m.ptr, np_, scale, n, k, 0, n, idx.ptr, d2.ptr, cnt.ptr)
+    call("grid_knn_topk_d2", dev.ctx, d2m.ptr, np_, 1.0, n, k, 0, n, idx.ptr, d2.ptr, cnt.ptr)
     return idx.numpy(), d2.numpy(), cnt.numpy()
 
 

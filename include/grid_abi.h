@@ -359,9 +359,11 @@ int grid_knn_dist_i32(grid_ctx *ctx, const int32_t *d_z, int64_t n, int64_t r, i
                       int64_t np_);
 int grid_knn_dist_f64(grid_ctx *ctx, const double *d_z, int64_t n, int64_t r, int64_t ld, double *d_d2,
                       int64_t np_);
-/* Row top-k on d2 rows (d_d2rows[r*ld + j] = d2(row0 + r, j)), ordered by
- * (floor(d2 * key_scale), j) with floor(d2 * key_scale) < 2^44: key_scale =
- * 1 keeps exact integer distances exact; d_d2 receives the d2 values. */
+/* Row top-k on d2 rows (d_d2rows[r*ld + j] = d2(row0 + r, j)), ordered
+ * exactly by (d2 as fp64, j) for finite d2 >= 0 (-0.0 counts as 0), ties in d2
+ * by the smaller j; d_d2 receives the d2 values.  key_scale (> 0) no longer
+ * takes part in the order -- no key is shortened -- and stays in the
+ * signature for callers of the earlier fixed-point key. */
 int grid_knn_topk_d2(grid_ctx *ctx, const double *d_d2rows, int64_t ld, double key_scale, int64_t n,
                      int64_t k, int64_t row0, int64_t nrows, int32_t *d_idx, double *d_d2,
                      int32_t *d_cnt);

@@ -36,7 +36,7 @@ def cohort():
     return q, reads, offs, np.array(nbr, dtype=np.int32), np.ones(len(nbr))
 
 
-def run_chain(rank, world, comm, lane, split="bin", piece_bytes=1 << 31):
+def run_chain(rank, world, comm, lane, split="bin", piece_bytes=1 << 31, k=K):
     from grid_amd import _abi
     from grid_amd.fused import HipOps, Steps47, TorchAlloc, shard_range
     q, reads, off, nbr, w = cohort()
@@ -53,7 +53,7 @@ def run_chain(rank, world, comm, lane, split="bin", piece_bytes=1 << 31):
             pdev.set_stream(ps)
             pl.append((HipOps(pdev), ps))
         pl = pl[0] if lane == 1 else pl
-    st = Steps47(HipOps(dev), TorchAlloc(0), N, M, c0, c1 - c0, k=K, n_nbr=4, n_iters=ITERS, comm=comm,
+    st = Steps47(HipOps(dev), TorchAlloc(0), N, M, c0, c1 - c0, k=k, n_nbr=4, n_iters=ITERS, comm=comm,
                  phase_lane=pl, split=split, piece_bytes=piece_bytes)
     st.set_reads(reads)
     st.set_phasing_graph(off, nbr, w)
@@ -70,12 +70,12 @@ def run_chain(rank, world, comm, lane, split="bin", piece_bytes=1 << 31):
     }
 
 
-def _worker(rank, world, port, out_path, split="bin", piece_bytes=1 << 31):
+def _worker(rank, world, port, out_path, split="bin", piece_bytes=1 << 31, k=K):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from grid_amd.fused import TorchComm
     res = run_chain(rank, world, TorchComm(dist), lane=2 if world % 2 == 0 else 1, split=split,
-                    piece_bytes=piece_bytes)
+                    piece_bytes=piece_bytes, k=k)
     np.savez(f"{out_path}.{rank}.npz", **{k: np.asarray(v) for k, v in res.items()})
     dist.barrier()
     dist.destroy_process_group()
@@ -94,10 +94,10 @@ def single():
     return run_chain(0, 1, None, lane=False)
 
 
-def _run(world, tmp_path, split="bin", piece_bytes=1 << 31):
+def _run(world, tmp_path, split="bin", piece_bytes=1 << 31, k=K):
     port = _free_port()
     out = str(tmp_path / "res")
-    mp.start_processes(_worker, args=(world, port, out, split, piece_bytes), nprocs=world, join=True,
+    mp.start_processes(_worker, args=(world, port, out, split, piece_bytes, k), nprocs=world, join=True,
                        start_method="spawn")
     return [dict(np.load(f"{out}.{r}.npz")) for r in range(world)]
 
@@ -114,6 +114,40 @@ def test_gpu_sharded_equals_single(single, world, tmp_path):
                                          (8, 1 << 31)])
 def test_gpu_cohort_split_equals_single(single, world, piece, tmp_path):
     _check(_run(world, tmp_path, split="cohort", piece_bytes=piece), single)
+
+
+@pytest.fixture(scope="module")
+def oracle_qz():
+    """The step-5 input by the oracle: the printed step-4 values ("%.2f" as
+    integer hundredths, tests/cpu_ops._hundredths, instead of formatting and
+    parsing 18 M cells) of the columns the printed ratios keep, clipped to
+    +-2.00, NaN -> 0 (find_neighbors.py:57-58)."""
+    from oracle import steps
+    from tests.cpu_ops import MISSING, NEG0, _hundredths
+    q = cohort()[0]
+    mat = np.where(q == -(2 ** 31), np.nan, q / 100.0)
+    z, ratios, mu, var, _ = steps.normalize_matrix(mat)
+    sel = steps.select_high_variance_regions(ratios, 0.1)
+    head = steps.normalized_lines(z, [], sel, mu, var, [])           # the two header lines only
+    _, r5, _, _ = steps.parse_normalized(head)
+    idx5, _ = steps.filter_regions_by_variance(r5, 1.0, 1000.0)
+    h = _hundredths(z[:, np.asarray(sel)[idx5]])
+    return np.where((h == MISSING) | (h == NEG0), 0, np.clip(h, -200, 200)).astype(np.int64)
+
+
+# k + 1 > SEG_K1: every rank selects from whole rows of the all-reduced Gram
+# (Steps47.full_rows), with the 32-key kernel at k = 20 and the radix kernel at
+# k = 40; the one-rank run they must equal is itself held to the oracle's k-NN
+@pytest.mark.parametrize("world,k", [(2, 20), (4, 40)])
+def test_gpu_full_rows_equals_single_and_oracle(oracle_qz, world, k, tmp_path):
+    from oracle import steps
+    one = run_chain(0, 1, None, lane=False, k=k)
+    nb = steps.knn_exact(oracle_qz, k)
+    assert one["idx"].shape == (N, k)
+    for i in range(N):
+        assert one["idx"][i].tolist() == [j for j, _ in nb[i]], i
+        assert one["d2"][i].tolist() == [s for _, s in nb[i]], i
+    _check(_run(world, tmp_path, k=k), one)
 
 
 def _check(parts, single):

@@ -43,14 +43,15 @@ def cohort(n=N, m=M):
     return q, reads, offs, np.array(nbr, dtype=np.int32), np.ones(len(nbr))
 
 
-def run_chain(rank, world, comm, chunk=None, source="resident", shape=(N, M), split="bin", piece_bytes=1 << 31):
+def run_chain(rank, world, comm, chunk=None, source="resident", shape=(N, M), split="bin", piece_bytes=1 << 31,
+              k=K):
     from grid_amd.fused import HostSource, Steps47, TorchAlloc, shard_range
     from tests.cpu_ops import NumpyOps
     N, M = shape
     q, reads, off, nbr, w = cohort(N, M)
     c0, c1 = shard_range(M, rank, world)
     qs = torch.from_numpy(np.ascontiguousarray(q[:, c0:c1]))
-    st = Steps47(NumpyOps(), TorchAlloc("cpu"), N, M, c0, c1 - c0, k=K, n_nbr=3, n_iters=ITERS, comm=comm,
+    st = Steps47(NumpyOps(), TorchAlloc("cpu"), N, M, c0, c1 - c0, k=k, n_nbr=3, n_iters=ITERS, comm=comm,
                  chunk=chunk, split=split, piece_bytes=piece_bytes)
     st.set_reads(reads)
     st.set_phasing_graph(off, nbr, w)
@@ -65,12 +66,13 @@ def run_chain(rank, world, comm, chunk=None, source="resident", shape=(N, M), sp
     }
 
 
-def _worker(rank, world, port, out_path, chunk, shape=(N, M), split="bin", piece_bytes=1 << 31):
+def _worker(rank, world, port, out_path, chunk, shape=(N, M), split="bin", piece_bytes=1 << 31, k=K):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.set_num_threads(1)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from grid_amd.fused import TorchComm
-    res = run_chain(rank, world, TorchComm(dist), chunk=chunk, shape=shape, split=split, piece_bytes=piece_bytes)
+    res = run_chain(rank, world, TorchComm(dist), chunk=chunk, shape=shape, split=split, piece_bytes=piece_bytes,
+                    k=k)
     np.savez(f"{out_path}.{rank}.npz", **{k: np.asarray(v) for k, v in res.items()})
     dist.barrier()
     dist.destroy_process_group()
@@ -116,10 +118,10 @@ def single_wide():
     return run_chain(0, 1, None, shape=WIDE)
 
 
-def _run_world(world, chunk, shape, tmp_path, split="bin", piece_bytes=1 << 31):
+def _run_world(world, chunk, shape, tmp_path, split="bin", piece_bytes=1 << 31, k=K):
     port = _free_port()
     out = str(tmp_path / "res")
-    mp.start_processes(_worker, args=(world, port, out, chunk, shape, split, piece_bytes), nprocs=world, join=True,
+    mp.start_processes(_worker, args=(world, port, out, chunk, shape, split, piece_bytes, k), nprocs=world, join=True,
                        start_method="spawn")
     return [dict(np.load(f"{out}.{r}.npz")) for r in range(world)]
 
@@ -173,6 +175,48 @@ def test_wide_single_rank_matches_oracle_neighbours(single_wide):
     nb = steps.knn_exact(qz, K)
     for i in range(WIDE[0]):
         assert single_wide["idx"][i, : len(nb[i])].tolist() == [j for j, _ in nb[i]], i
+
+
+# k + 1 > SEG_K1 (Steps47.full_rows): the bin split all-reduces the whole Gram
+# and every rank selects from full rows; n = 48 > k + 1, so k + 1 keys are taken
+FULL = (48, M)
+K_FULL = 20
+
+
+@pytest.fixture(scope="module")
+def single_full():
+    return run_chain(0, 1, None, shape=FULL, k=K_FULL)
+
+
+def test_full_rows_single_rank_matches_oracle_neighbours(single_full):
+    from oracle import steps
+    q = cohort(*FULL)[0]
+    mat = np.where(q == -(2 ** 31), np.nan, q / 100.0)
+    z, ratios, mu, var, _ = steps.normalize_matrix(mat)
+    sel = steps.select_high_variance_regions(ratios, 0.1)
+    assert single_full["sel"].tolist() == sel
+    lines = steps.normalized_lines(z, [f"S{i}" for i in range(FULL[0])], sel, mu, var, np.nanmean(mat, axis=1))
+    _, r5, z5, _ = steps.parse_normalized(lines)
+    idx5, _ = steps.filter_regions_by_variance(r5, 1.0, 1000.0)
+    qz = np.rint(np.nan_to_num(np.clip(z5, -2.0, 2.0), nan=0.0)[:, idx5] * 100).astype(np.int64)
+    nb = steps.knn_exact(qz, K_FULL)
+    assert single_full["idx"].shape == (FULL[0], K_FULL)
+    for i in range(FULL[0]):
+        assert single_full["idx"][i].tolist() == [j for j, _ in nb[i]], i
+        assert single_full["d2"][i].tolist() == [s for _, s in nb[i]], i
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_full_rows_equals_single(single_full, world, tmp_path):
+    _check_parts(_run_world(world, None, FULL, tmp_path, k=K_FULL), single_full)
+
+
+def test_cohort_split_rejects_full_rows():
+    """The cohort split has no whole Gram to select from: k + 1 > SEG_K1 raises."""
+    from grid_amd._abi import GridNativeError
+    from grid_amd.fused import SimComm
+    with pytest.raises(GridNativeError, match="cohort split needs k"):
+        run_chain(0, 2, SimComm(2, 0), shape=FULL, split="cohort", k=K_FULL)
 
 
 def _check_parts(parts, single):
