@@ -151,6 +151,10 @@ _SIGS = {
                           C.POINTER(_i64), C.POINTER(_i32)],
     "grid_md_parse_map": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                           _vp, _vp],
+    "grid_md_parse_ref_general": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                  C.POINTER(_i64)],
+    "grid_md_parse_map_general": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                  _vp, _vp, _vp],
     "grid_fill_i32": [_vp, _vp, _i64, _i32],
     "grid_md_finish": [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)],
     "grid_md_gather": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
@@ -483,6 +487,11 @@ class DevBuf:
         call("grid_d2h", self.dev.ctx, out.ctypes.data, self.ptr, self.nbytes)
         return out
 
+    def __array__(self, dtype=None, copy=None):
+        # np.asarray(buf): a host copy (the device ingest's matrix where a caller expects the host parser's)
+        a = self.numpy()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
     def copy_from(self, a: np.ndarray):
         a = np.ascontiguousarray(a, dtype=self.dtype)
         assert a.nbytes <= self.nbytes
@@ -811,7 +820,7 @@ class MdOpts(C.Structure):
                 ("d_mask_name_off", C.c_void_p), ("d_mask_kb_off", C.c_void_p), ("d_mask_kb", C.c_void_p)]
 
 
-MD_EXOTIC, MD_NOTINK = 1, 2
+MD_EXOTIC, MD_NOTINK, MD_LINES = 1, 2, 4
 
 
 def gz_text_size(buf) -> tuple[int, int] | None:

@@ -219,11 +219,19 @@ struct PadText {
   __device__ __forceinline__ uint8_t operator[](int k) const { return t[md_phys(i0 + k)]; }
 };
 
+// general keys (MODE 2 / 3 below): the tag of line idx of its file, and the
+// last line number that has one (a tag stays below 0)
+constexpr int64_t MD_TAG_MAXLINE = 0x7fffffffLL - 3;
+__device__ __forceinline__ int32_t md_tag(int64_t idx) { return (int32_t)(GRID_MISSING + 1 + (int32_t)idx); }
+
 // MODE 0 (reference file): kept[i] = 1 and keys[i] = (s, e) for every line i
 // that passes the prefix, window and mask tests, whatever its depth (a bin
 // the reference sample did not cover can be covered by another sample; a key
 // no file keeps gets count 0 and is never valid).  MODE 1 (map): every line
-// that also has depth > 0: Q[row(f)][K index] = q, kept[f] += 1.
+// that also has depth > 0: Q[row(f)][K index] = q, kept[f] += 1.  MODE 2 and
+// 3 (general keys: a file may repeat a key, its last kept line wins): the same
+// lines as MODE 1 in two launches over the same text, 2 the tag pass (counts
+// nothing), 3 the resolve pass (kept[f] += 1 per cell it fills).
 //
 // One workgroup per 64 KiB chunk: the chunk (and 16 bytes before it, up to
 // MAXLINE after it) is loaded into LDS with 16-byte loads all in flight; each
@@ -362,9 +370,24 @@ __global__ __launch_bounds__(PTH) __attribute__((amdgpu_waves_per_eu(GRID_MDPARS
       }
       if (j < 0) {
         bad |= GRID_MD_NOTINK;
-      } else {
+      } else if (MODE == 1) {
         Q[(int64_t)qrow[f] * ldq + j] = (int32_t)q;
         nkept++;
+      } else if (idx > MD_TAG_MAXLINE) {
+        bad |= GRID_MD_LINES;
+      } else {
+        // general keys: the cell goes to the LAST kept line of its key.  The
+        // tag pass leaves the largest line number of the key in the cell (as
+        // a tag: negative, above GRID_MISSING, so never a depth, which is
+        // > 0); the resolve pass stores the depth of the line whose tag it is
+        int32_t *cell = Q + (int64_t)qrow[f] * ldq + j;
+        const int32_t tag = md_tag(idx);
+        if (MODE == 2) {
+          atomicMax(cell, tag);
+        } else if (*cell == tag) {
+          *cell = (int32_t)q;
+          nkept++;
+        }
       }
     }
   };
@@ -397,7 +420,7 @@ __global__ __launch_bounds__(PTH) __attribute__((amdgpu_waves_per_eu(GRID_MDPARS
     }
   }
   if (bad) atomicOr(flags + f, bad);
-  if (MODE == 1) {
+  if (MODE == 1 || MODE == 3) {
     for (int k = 32; k > 0; k >>= 1) nkept += __shfl_xor(nkept, k, 64);
     if ((tid & 63) == 0 && nkept) atomicAdd(kept + f, nkept);
   }
@@ -427,6 +450,50 @@ __global__ void k_md_sorted(const Key2 *__restrict__ K, int64_t nK, int32_t *__r
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j + 1 >= nK) return;
   if (!key_lt(K[j].s, K[j].e, K[j + 1])) atomicOr(bad, 1);
+}
+
+// ---- the general reference index: K = the kept keys sorted and de-duplicated ----
+// kept lines in line order -> their starts, ends and line numbers, packed
+__global__ void k_md_gk_pack(const uint8_t *__restrict__ kept, const int64_t *__restrict__ pos, int64_t n,
+                             const Key2 *__restrict__ keys, int64_t *__restrict__ ps, int64_t *__restrict__ pe,
+                             int32_t *__restrict__ pline, int32_t *__restrict__ iota, int32_t *__restrict__ kidx) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  kidx[i] = -1;
+  if (kept[i]) {
+    const int64_t p = pos[i];
+    ps[p] = keys[i].s;
+    pe[p] = keys[i].e;
+    pline[p] = (int32_t)i;
+    iota[p] = (int32_t)p;
+  }
+}
+
+__global__ void k_md_gk_take(const int64_t *__restrict__ src, const int32_t *__restrict__ perm, int64_t n,
+                             int64_t *__restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[perm[i]];
+}
+
+// sorted position i holds packed record perm[i]: 1 where its key differs from its predecessor's
+__global__ void k_md_gk_heads(const int64_t *__restrict__ ss, const int64_t *__restrict__ pe,
+                              const int32_t *__restrict__ perm, int64_t n, int32_t *__restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  head[i] = i == 0 || ss[i] != ss[i - 1] || pe[perm[i]] != pe[perm[i - 1]];
+}
+
+// rank = heads before i (+ its own) - 1: K[rank] at the heads, kidx[line] = rank for every kept line
+__global__ void k_md_gk_index(const int64_t *__restrict__ ss, const int64_t *__restrict__ pe,
+                              const int32_t *__restrict__ perm, const int32_t *__restrict__ pline,
+                              const int32_t *__restrict__ head, const int64_t *__restrict__ hpos, int64_t n,
+                              Key2 *__restrict__ K, int32_t *__restrict__ kidx) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = perm[i];
+  const int64_t rank = hpos[i] + head[i] - 1;
+  if (head[i]) K[rank] = Key2{ss[i], pe[r]};
+  kidx[pline[r]] = (int32_t)rank;
 }
 
 __global__ void k_fill_i32(int32_t *__restrict__ p, int64_t n, int32_t v) {
@@ -653,6 +720,94 @@ int grid_md_parse_ref(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_tof
   HIPCHK(hipFreeAsync(pos, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   *h_nK = nK;
+  return GRID_OK;
+}
+
+int grid_md_parse_ref_general(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                              int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart,
+                              const int64_t *d_cline0, const grid_md_opts *opts, int32_t *d_flags, int64_t nlines,
+                              uint8_t *d_kept_line, void *d_keys_line, void *d_K, int32_t *d_kidx, int64_t *h_nK) {
+  REQUIRE(ctx && opts && h_nK && nlines >= 0 && nlines < (1ll << 31) && nchunks >= 0, "bad args");
+  *h_nK = 0;
+  if (nlines == 0 || nchunks == 0) return GRID_OK;
+  HIPCHK(hipMemsetAsync(d_kept_line, 0, (size_t)nlines, ctx->stream));
+  hipLaunchKernelGGL(k_md_parse<0>, dim3((unsigned)nchunks), dim3(PTH), 0, ctx->stream, d_text, d_toff, d_tlen,
+                     d_cfile, d_cstart, d_cline0, to_opts(opts), d_flags, d_kept_line, (Key2 *)d_keys_line, nlines,
+                     nullptr, (int64_t)0, nullptr, (int64_t)0, nullptr, (int64_t)0, nullptr, nullptr, nullptr);
+  LAUNCHCHK();
+  // one block: the scan's positions, then the packed records and the sorts' arrays
+  const size_t nl8 = ((size_t)nlines * 8 + 255) & ~size_t(255), nl4 = ((size_t)nlines * 4 + 255) & ~size_t(255);
+  char *blk = nullptr;
+  HIPCHK(hipMallocAsync((void **)&blk, 6 * nl8 + 5 * nl4 + 1024, ctx->stream));
+  struct Free {
+    grid_ctx *c;
+    void *p;
+    ~Free() { (void)hipFreeAsync(p, c->stream); }
+  } guard{ctx, blk};
+  int64_t *pos = (int64_t *)blk, *ps = (int64_t *)(blk + nl8), *pe = (int64_t *)(blk + 2 * nl8),
+          *ta = (int64_t *)(blk + 3 * nl8), *ss = (int64_t *)(blk + 4 * nl8), *hpos = (int64_t *)(blk + 5 * nl8);
+  char *b4 = blk + 6 * nl8;
+  int32_t *pline = (int32_t *)b4, *iota = (int32_t *)(b4 + nl4), *perm1 = (int32_t *)(b4 + 2 * nl4),
+          *perm2 = (int32_t *)(b4 + 3 * nl4), *head = (int32_t *)(b4 + 4 * nl4);
+  int rc = excl_scan(ctx, d_kept_line, pos, nlines);
+  if (rc) return rc;
+  int64_t last_pos = 0;
+  uint8_t last_kept = 0;
+  HIPCHK(hipMemcpyAsync(&last_pos, pos + nlines - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&last_kept, d_kept_line + nlines - 1, 1, hipMemcpyDeviceToHost, ctx->stream));
+  const unsigned gl = (unsigned)((nlines + 255) / 256);
+  hipLaunchKernelGGL(k_md_gk_pack, dim3(gl), dim3(256), 0, ctx->stream, d_kept_line, pos, nlines,
+                     (const Key2 *)d_keys_line, ps, pe, pline, iota, d_kidx);
+  LAUNCHCHK();
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int64_t n = last_pos + last_kept;             // kept lines
+  if (n == 0) return GRID_OK;
+  // order by (s, e): two stable pair sorts, by e and then by s (the grammar's
+  // values are < 10^18 < 2^60, never negative)
+  size_t tmp = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, pe, ta, iota, perm1, (int)n, 0, 60, ctx->stream));
+  void *s = nullptr;
+  rc = grid_scratch(ctx, tmp + 256, &s);
+  if (rc) return rc;
+  const unsigned gn = (unsigned)((n + 255) / 256);
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(s, tmp, pe, ta, iota, perm1, (int)n, 0, 60, ctx->stream));
+  hipLaunchKernelGGL(k_md_gk_take, dim3(gn), dim3(256), 0, ctx->stream, ps, perm1, n, ta);
+  LAUNCHCHK();
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(s, tmp, ta, ss, perm1, perm2, (int)n, 0, 60, ctx->stream));
+  hipLaunchKernelGGL(k_md_gk_heads, dim3(gn), dim3(256), 0, ctx->stream, ss, pe, perm2, n, head);
+  LAUNCHCHK();
+  rc = excl_scan(ctx, head, hpos, n);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_md_gk_index, dim3(gn), dim3(256), 0, ctx->stream, ss, pe, perm2, pline, head, hpos, n,
+                     (Key2 *)d_K, d_kidx);
+  LAUNCHCHK();
+  int64_t lh = 0;
+  int32_t lf = 0;
+  HIPCHK(hipMemcpyAsync(&lh, hpos + n - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(&lf, head + n - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *h_nK = lh + lf;
+  return GRID_OK;
+}
+
+int grid_md_parse_map_general(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                              int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart,
+                              const int64_t *d_cline0, const grid_md_opts *opts, int32_t *d_flags, const void *d_K,
+                              int64_t nK, const int32_t *d_kidx, int64_t ref_nlines, int32_t *d_Q, int64_t ldq,
+                              const int32_t *d_qrow, uint64_t *d_kept, const int32_t *d_fstatus) {
+  REQUIRE(ctx && opts && nchunks >= 0 && nK >= 0 && ldq >= nK, "bad args");
+  if (nchunks == 0) return GRID_OK;
+  // the tag pass, then the resolve pass behind it on the stream, over the same text
+  hipLaunchKernelGGL(k_md_parse<2>, dim3((unsigned)nchunks), dim3(PTH), 0, ctx->stream, d_text, d_toff, d_tlen,
+                     d_cfile, d_cstart, d_cline0, to_opts(opts), d_flags, nullptr, nullptr, (int64_t)0,
+                     (const Key2 *)d_K, nK, d_kidx, ref_nlines, d_Q, ldq, d_qrow, (unsigned long long *)d_kept,
+                     d_fstatus);
+  LAUNCHCHK();
+  hipLaunchKernelGGL(k_md_parse<3>, dim3((unsigned)nchunks), dim3(PTH), 0, ctx->stream, d_text, d_toff, d_tlen,
+                     d_cfile, d_cstart, d_cline0, to_opts(opts), d_flags, nullptr, nullptr, (int64_t)0,
+                     (const Key2 *)d_K, nK, d_kidx, ref_nlines, d_Q, ldq, d_qrow, (unsigned long long *)d_kept,
+                     d_fstatus);
+  LAUNCHCHK();
   return GRID_OK;
 }
 

@@ -11,7 +11,10 @@ Here the cohort is split twice:
   * by FILES for the ingest -- rank r inflates and parses a contiguous slice
     of the files (in file order, balanced by compressed bytes) into its own
     [files][K] int32 hundredths matrix over the reference key list K (rank 0
-    reads K from the first batch and broadcasts it);
+    reads K from the first batch and broadcasts it, with the key mode: when
+    the reference file's keys repeat or are unsorted, rank 0 reads K again
+    in the device ingest's general key mode and every rank parses its slice
+    in that mode -- the last kept line of a key wins, as in the reference);
   * the population means (:218-301, fp64 sums in file order) are a chain
     over the ranks: rank r continues rank r-1's (sum, count) over its rows
     and passes them on (grid_md_popsum, point-to-point), the last rank's
@@ -168,7 +171,9 @@ def make_backend(config):
     if BACKEND_FACTORY is not None:
         return BACKEND_FACTORY(config)
     from ..device import get_device
-    return HipBackend(get_device(config))
+    from .normalize_mosdepth import DEVICE_KEYS_DEFAULT, check_device_keys
+    norm = (config or {}).get("mosdepth", {}).get("normalize", {})
+    return HipBackend(get_device(config), check_device_keys(norm.get("device_keys", DEVICE_KEYS_DEFAULT)))
 
 
 class HipBackend:
@@ -176,11 +181,13 @@ class HipBackend:
     the grid_md_* chain kernels, fused.HipOps for steps 4-5, the device
     writer.  Torch tensors and the library's kernels share one stream."""
 
-    def __init__(self, dev):
+    def __init__(self, dev, device_keys="auto"):
         import torch
         from ..fused import HipOps, TorchAlloc
         self.torch = torch
         self.dev = dev
+        self.device_keys = device_keys          # mosdepth.normalize.device_keys: auto, strict, general
+        self.key_mode = 0                       # the ingest's key mode on every rank: 0 strict, 1 general
         self.stream = torch.cuda.Stream(device=dev.index)
         dev.set_stream(self.stream)
         self.alloc = TorchAlloc(dev.index)
@@ -190,14 +197,32 @@ class HipBackend:
         return self.torch.cuda.stream(self.stream)
 
     def ref_keys(self, paths, prefix, window, excluded, min_depth, max_depth, threads):
+        """(K, kidx, ref_nlines, key mode) or None; strict keys first, the
+        general key mode when the reference file's keys are not strictly
+        increasing (unless the config says strict)."""
         from . import ingest_device
-        return ingest_device.ingest_device(self.dev, paths, prefix, window, excluded, min_depth, max_depth,
-                                           threads=threads, keys_only=True)
+
+        def run(keys):
+            return ingest_device.ingest_device(self.dev, paths, prefix, window, excluded, min_depth, max_depth,
+                                               threads=threads, keys_only=True, keys=keys)
+        mode = 1 if self.device_keys == "general" else 0
+        try:
+            ref = run("general" if mode else "strict")
+        except ingest_device.DeviceIngestKeys:
+            if self.device_keys == "strict":
+                raise
+            mode = 1
+            ref = run("general")
+        return None if ref is None else (*ref, mode)
+
+    def set_key_mode(self, mode):
+        self.key_mode = int(mode)
 
     def ingest(self, paths, ref, prefix, window, excluded, min_depth, max_depth, threads):
         from . import ingest_device
         Q, nK, status, kept = ingest_device.ingest_device(self.dev, paths, prefix, window, excluded, min_depth,
-                                                          max_depth, threads=threads, ref=ref, finish=False)
+                                                          max_depth, threads=threads, ref=ref, finish=False,
+                                                          keys="general" if self.key_mode else "strict")
         return Q, status, kept
 
     def free(self, Q):
@@ -326,9 +351,12 @@ def normalize_dist(comm, backend, *, individuals, mosdepth_dir, chromosome, star
             ok = False
     if not agree(comm, ok):
         raise DistFallback("reference keys")
-    hdr = _ctl(comm, [-1, 0] if ref is None else [len(ref[0]), int(ref[2])])
+    # the key mode travels with the header (a backend whose ref_keys gives 3 values: mode 0)
+    hdr = _ctl(comm, [-1, 0, 0] if ref is None else [len(ref[0]), int(ref[2]), int(ref[3]) if len(ref) > 3 else 0])
     comm.broadcast(hdr, 0)
-    nK, ref_nlines = (int(x) for x in hdr.cpu().numpy())
+    nK, ref_nlines, key_mode = (int(x) for x in hdr.cpu().numpy())
+    if hasattr(backend, "set_key_mode"):
+        backend.set_key_mode(key_mode)
     if nK < 0:
         return None                                  # no file inflates: no samples (every rank)
     Kt = backend.alloc.empty((max(nK, 1), 2), I8)

@@ -27,13 +27,28 @@ equal the CRC its gzip trailers give (the GPU-inflated members are checked the
 same way by grid_gunzip_batch's k_gz_crc); a mismatch hands the cohort to the
 host parser.
 
-Anything outside the common shape -- a line outside the canonical mosdepth
-grammar or a non-ASCII byte, reference keys that are not strictly
-increasing, a key outside K, a repeated key, a file of plain gzip members
-whose total size its trailer does not give -- raises DeviceIngestUnsupported
-and the caller reads the cohort with the host parser (ingest.cpp), which
-covers every case the reference reads.  A file that does not inflate (corrupt,
-truncated, not gzip) is dropped as the reference drops it.
+Two key modes (``keys=``).  "strict", the fast common case: the reference
+file's kept (start, end) keys are strictly increasing in line order and no
+file repeats a key; otherwise DeviceIngestKeys (a DeviceIngestUnsupported).
+"general", the reference's own semantics for any order and any repeats (its
+raw ``startswith("chr1")`` also keeps the lines of chr10..chr19, whose bins
+repeat chr1's coordinates): the columns are the sorted, de-duplicated kept keys
+of the reference file (grid_md_parse_ref_general) and within a file a key takes
+the value of the LAST line in file order that passes every filter
+(grid_md_parse_map_general: a tag pass and a resolve pass over the same text,
+no memory beyond the matrix).  normalize_mosdepth.ingest tries strict first and
+general on DeviceIngestKeys (config ``mosdepth.normalize.device_keys``).
+
+What still hands over in either mode -- a line outside the canonical mosdepth
+grammar or a non-ASCII byte, a key outside K, text in HBM that does not match
+its gzip CRC, a file of plain gzip members whose total size its trailer does
+not give, a reference file that keeps no record; in strict mode reference keys
+that are not strictly increasing or a repeated key (DeviceIngestKeys); in
+general mode a file of more than 2^31 - 3 lines -- raises
+DeviceIngestUnsupported and the caller reads the cohort with the host parser
+(ingest.cpp), which covers every case the reference reads.  A file that does
+not inflate (corrupt, truncated, not gzip) is dropped as the reference drops
+it.
 """
 from __future__ import annotations
 
@@ -88,6 +103,23 @@ def host_frac(threads):
 
 class DeviceIngestUnsupported(Exception):
     """The cohort leaves the device parser's common case (see the module doc)."""
+
+
+class DeviceIngestKeys(DeviceIngestUnsupported):
+    """Strict key mode only: the reference file's keys are not strictly
+    increasing, or a file repeats a key -- what the general key mode reads."""
+
+
+KEY_MODES = ("strict", "general")
+
+
+def _flag_reason(flags):
+    """Why a file's parse flags hand the cohort over."""
+    if flags & _abi.MD_EXOTIC:
+        return "a line outside the mosdepth grammar"
+    if flags & _abi.MD_NOTINK:
+        return "a key outside K"
+    return "more than 2^31 - 3 lines (general keys)"
 
 
 def _align(x, a=256):
@@ -306,8 +338,11 @@ class _Async:
     lengths, flags and kept counts stay on the device per batch and are read
     once at the end (results)."""
 
-    def __init__(self, dev, cdev, opts, K, nK, kidx, ref_nlines, Q):
+    def __init__(self, dev, cdev, opts, K, nK, kidx, ref_nlines, Q, general=False):
         self.dev, self.cdev, self.opts = dev, cdev, opts
+        # general keys: the tag and the resolve pass (one call, two launches back
+        # to back on the stream, before `done`: the parity's text is still intact)
+        self.parse_map = "grid_md_parse_map_general" if general else "grid_md_parse_map"
         self.K, self.nK, self.kidx, self.ref_nlines, self.Q = K, nK, kidx, ref_nlines, Q
         self.h2d = [_abi.Event(), _abi.Event()]
         self.done = [_abi.Event(), _abi.Event()]
@@ -433,7 +468,7 @@ class _Async:
         if nch:
             call("grid_md_count", dev.ctx, d_text.ptr, d_toff, d_tl, nch, d_cf, d_cs, d_c1, len(okb), cnl.ptr,
                  cline0.ptr, bflags.ptr, fst.ptr)
-            call("grid_md_parse_map", dev.ctx, d_text.ptr, d_toff, d_tl, nch, d_cf, d_cs, cline0.ptr,
+            call(self.parse_map, dev.ctx, d_text.ptr, d_toff, d_tl, nch, d_cf, d_cs, cline0.ptr,
                  C.byref(self.opts), bflags.ptr, self.K.ptr, self.nK, self.kidx.ptr, self.ref_nlines, self.Q.ptr,
                  self.nK, d_qrow, bk.ptr, fst.ptr)
         self.done[p].put(dev)
@@ -467,8 +502,7 @@ class _Async:
             bf, bkv = bflags.numpy(), bk.numpy()
             for k in okb:
                 if bad[k] == 0 and bf[k]:
-                    why = "a line outside the mosdepth grammar" if bf[k] & _abi.MD_EXOTIC else "a key outside K"
-                    raise DeviceIngestUnsupported(f"{paths[fs[k]]}: {why}")
+                    raise DeviceIngestUnsupported(f"{paths[fs[k]]}: {_flag_reason(int(bf[k]))}")
             for k, f in enumerate(fs):
                 res.append((f, 0 if bad[k] == 0 else 1, int(bkv[k])))
             self.kept.append((np.asarray(fs), bkv))
@@ -493,7 +527,7 @@ class _Async:
 
 
 def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, threads=16, ref=None,
-                  keys_only=False, finish=True):
+                  keys_only=False, finish=True, keys="strict"):
     """paths: one per individual in file order (None = no file).  Returns
     (ok files in file order, the device state for ``gather``, records in valid
     columns per file, status per file: 0 ok, 1 failed, 3 missing); raises
@@ -505,7 +539,17 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
     inflates), every rank then parses its slice of the files over that K
     (``ref``) with ``finish=False``: (Q [nfiles][nK] int32 on the device, nK,
     status, records kept per file) -- the population means are a chain over
-    the ranks there."""
+    the ranks there.
+
+    keys: "strict" (the reference file's keys strictly increasing, no key
+    repeated in a file, else DeviceIngestKeys) or "general" (any order, any
+    repeats: sorted unique columns, the last kept line of a key wins; see the
+    module doc).  ``keys_only`` and ``ref`` work in either mode, and a ``ref``
+    from one mode must be parsed in the same mode."""
+    if keys not in KEY_MODES:
+        raise ValueError(f"keys must be one of {KEY_MODES}, not {keys!r}")
+    general = keys == "general"
+    parse_map = "grid_md_parse_map_general" if general else "grid_md_parse_map"
     nfiles = len(paths)
     t_start = time.perf_counter()
     keep = []
@@ -731,7 +775,7 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
                 # every file BGZF (what mosdepth writes): the GPU inflates all of
                 # them, and the batch is enqueued behind the previous one
                 if pipe is None:
-                    pipe = _Async(dev, cdev, opts, K, nK, kidx, ref_nlines, Q)
+                    pipe = _Async(dev, cdev, opts, K, nK, kidx, ref_nlines, Q, general=general)
                 hshare = None
                 if hfrac > 0 and len(todo) > 1:
                     # every step-th file to the host threads (they start now, beside the
@@ -798,12 +842,20 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
                 kidx = dev.alloc(max(ref_nlines, 1), np.int32)
                 h_nK, h_uns = C.c_int64(), C.c_int32()
                 d_rcf, d_rcs, d_rcl = dev.upload(rc_file), dev.upload(cstart[c0:c1]), dev.upload(cl)
-                call("grid_md_parse_ref", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
-                     d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
-                     kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK), C.byref(h_uns))
+                if general:
+                    if ref_nlines >= 1 << 31:
+                        raise DeviceIngestUnsupported(f"{paths[fs[r]]}: {_flag_reason(_abi.MD_LINES)}")
+                    # K: the kept keys sorted and de-duplicated, any order, any repeats
+                    call("grid_md_parse_ref_general", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
+                         d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
+                         kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK))
+                else:
+                    call("grid_md_parse_ref", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
+                         d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
+                         kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK), C.byref(h_uns))
                 del kline, keys_line
                 if h_uns.value:
-                    raise DeviceIngestUnsupported("the reference file's keys are not strictly increasing")
+                    raise DeviceIngestKeys("the reference file's keys are not strictly increasing")
                 nK = h_nK.value
                 if nK == 0:
                     raise DeviceIngestUnsupported("the reference file keeps no record")
@@ -813,14 +865,13 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
                 call("grid_fill_i32", dev.ctx, Q.ptr, nfiles * nK, _abi.MISSING)
             qrow = dev.upload(np.asarray(fs, np.int32))
             bk = dev.zeros(nb, np.uint64)
-            call("grid_md_parse_map", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, nch, d_cfile.ptr, d_cstart.ptr,
+            call(parse_map, dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, nch, d_cfile.ptr, d_cstart.ptr,
                  cline0.ptr, C.byref(opts), bflags.ptr, K.ptr, nK, kidx.ptr, ref_nlines, Q.ptr, nK, qrow.ptr, bk.ptr,
                  None)
             bf, bkv = bflags.numpy(), bk.numpy()
             for k in okb:
                 if bf[k]:
-                    why = "a line outside the mosdepth grammar" if bf[k] & _abi.MD_EXOTIC else "a key outside K"
-                    raise DeviceIngestUnsupported(f"{paths[fs[k]]}: {why}")
+                    raise DeviceIngestUnsupported(f"{paths[fs[k]]}: {_flag_reason(int(bf[k]))}")
             kept_h = kept.numpy()
             kept_h[np.asarray(fs)] += bkv
             kept.copy_from(kept_h)
@@ -890,7 +941,10 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
          float(max_depth), mean.ptr, valid.ptr, cpos.ptr, present.ptr, nvalid.ptr, C.byref(m))
     pres, nval, kh = present.numpy()[:nfiles], nvalid.numpy()[:nfiles], kept.numpy()[:nfiles]
     if np.any(pres[rows] != kh[rows]):
-        raise DeviceIngestUnsupported("a repeated (start, end) key in a file")
+        if general:
+            # the integrity guard: every present cell was filled by exactly one line's resolve
+            raise DeviceIngestUnsupported("an unresolved cell in a file's row (general keys)")
+        raise DeviceIngestKeys("a repeated (start, end) key in a file")
     m = m.value
     if TRACE:
         import sys

@@ -300,20 +300,48 @@ def _read_all(individuals, mosdepth_dir, chromosome, start, end, excluded, threa
     return {k: v for k, v in res.items() if v is not None}
 
 
+DEVICE_KEYS = ("auto", "strict", "general")     # mosdepth.normalize.device_keys
+DEVICE_KEYS_DEFAULT = "auto"
+
+
+def check_device_keys(v):
+    if v not in DEVICE_KEYS:
+        raise ValueError(f"mosdepth.normalize.device_keys must be one of {', '.join(DEVICE_KEYS)}, not {v!r}")
+    return v
+
+
 def ingest(individuals, mosdepth_dir, chromosome, start, end, excluded, min_depth, max_depth, threads,
-           console=None, dev=None):
+           console=None, dev=None, device_keys=DEVICE_KEYS_DEFAULT):
     """R1-R4 (:218-416): mosdepth files -> (ids, regions, int32 hundredths).
     With a device (``dev``): inflated and parsed in HBM (ingest_device.py;
     the matrix is returned as a device buffer); the host C++ parser
     (``grid_ingest_*``, grid_amd/csrc/ingest.cpp) takes any cohort outside
     that path's common case, with one multithreaded parse per file; text that
     leaves the strict mosdepth grammar (or a non-integer window) goes through
-    the line-by-line restatement ``ingest_py``."""
+    the line-by-line restatement ``ingest_py``.
+
+    device_keys: the device ingest's key mode (ingest_device.py).  "strict":
+    reference keys strictly increasing and no key repeated in a file, else the
+    host parser; "general": repeated and unsorted keys read on the device (the
+    last kept line wins); "auto": strict first, general when the cohort has
+    such keys."""
+    check_device_keys(device_keys)
     ints = all(v is None or (isinstance(v, int) and not isinstance(v, bool)) for v in (start, end))
     if ints and dev is not None:
         try:
-            return _ingest_dev(dev, individuals, mosdepth_dir, chromosome, start, end, excluded, min_depth,
-                               max_depth, threads, console)
+            try:
+                return _ingest_dev(dev, individuals, mosdepth_dir, chromosome, start, end, excluded, min_depth,
+                                   max_depth, threads, console,
+                                   keys="general" if device_keys == "general" else "strict")
+            except ingest_device.DeviceIngestKeys as e:
+                if device_keys != "auto":
+                    raise
+                msg = (f"device mosdepth parser: {e}: the cohort has repeated or unsorted keys; "
+                       "using the general key mode")
+                log(console, msg, style="warning") if console else print(msg)
+                # again, over the cached device buffers and staging
+                return _ingest_dev(dev, individuals, mosdepth_dir, chromosome, start, end, excluded, min_depth,
+                                   max_depth, threads, console, keys="general")
         except ingest_device.DeviceIngestUnsupported as e:
             msg = f"device mosdepth parser: {e}; using the host parser"
             log(console, msg, style="warning") if console else print(msg)
@@ -336,9 +364,9 @@ def ingest(individuals, mosdepth_dir, chromosome, start, end, excluded, min_dept
 
 
 def _ingest_dev(dev, individuals, mosdepth_dir, chromosome, start, end, excluded, min_depth, max_depth, threads,
-                console=None):
+                console=None, keys="strict"):
     """R1-R4 on the device (ingest_device.py); same (ids, regions, matrix) as
-    ``ingest_native``, the matrix a device buffer."""
+    ``ingest_native``, the matrix a device buffer.  keys: the key mode."""
     import time
     t0 = time.perf_counter()
     inds = list(individuals)
@@ -349,7 +377,7 @@ def _ingest_dev(dev, individuals, mosdepth_dir, chromosome, start, end, excluded
         print(f"[ingest] paths in {time.perf_counter() - t0:.3f} s", file=sys.stderr, flush=True)
     rows, state, nval, status = ingest_device.ingest_device(
         dev, paths, norm_chrom(chromosome) if chromosome else None, window, excluded or {}, min_depth, max_depth,
-        threads=max(1, int(threads or 1)))
+        threads=max(1, int(threads or 1)), keys=keys)
     if ingest_device.TRACE:
         print(f"[ingest] device ingest returned at {time.perf_counter() - t0:.3f} s", file=sys.stderr, flush=True)
     keep = {ind: i for i, ind in enumerate(inds) if status[i] == 0 and state is not None and nval[i] > 0}
@@ -474,6 +502,7 @@ def normalize_mosdepth(config, console):
         max_depth = config["mosdepth"]["normalize"].get("max_depth", 100)
         top_frac = config["mosdepth"]["normalize"].get("top_frac", 0.1)
         repeat_mask = config["mosdepth"]["normalize"].get("repeat_mask_file", None)
+        check_device_keys(config["mosdepth"]["normalize"].get("device_keys", DEVICE_KEYS_DEFAULT))
     except Exception as e:
         log(console, f"[red]Config error: {e}[/red]")
         return
@@ -553,7 +582,8 @@ def _normalize_one(config, console, individuals, mosdepth_dir, chrom, start, end
     dev_ingest = bool(config["mosdepth"]["normalize"].get("device_ingest", True))
     with progress_bar(console, total=len(individuals), description="Extracting per-sample regions...") as (p, t):
         ids, regions, q = ingest(individuals, mosdepth_dir, chrom, start, end, excluded, min_depth, max_depth,
-                                 threads, console, dev=dev if dev_ingest else None)
+                                 threads, console, dev=dev if dev_ingest else None,
+                                 device_keys=config["mosdepth"]["normalize"].get("device_keys", DEVICE_KEYS_DEFAULT))
         p.update(t, completed=len(individuals))
     if not ids:
         log(console, "No valid samples with regions found.", style="danger")

@@ -661,6 +661,32 @@ int grid_md_parse_map(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_tof
                       const grid_md_opts *opts, int32_t *d_flags, const void *d_K, int64_t nK,
                       const int32_t *d_kidx, int64_t ref_nlines, int32_t *d_Q, int64_t ldq, const int32_t *d_qrow,
                       uint64_t *d_kept, const int32_t *d_fstatus);
+/* General keys: the reference's own semantics for files that repeat a (start, end) key or list
+ * keys out of order (its raw startswith("chr1") also keeps the lines of chr10..chr19, whose bins
+ * repeat chr1's coordinates; records are keyed by (start, end) alone and the last line wins).
+ * grid_md_parse_ref_general: as grid_md_parse_ref, but d_K is the SORTED, DE-DUPLICATED set of the
+ * reference file's kept keys (strictly increasing, *h_nK unique keys; two stable radix sorts of
+ * the kept (key, line) pairs, by end then by start, over the grammar's whole range) and
+ * d_kidx[line] = the K index of that line's key for every kept line, -1 otherwise.  nlines < 2^31. */
+int grid_md_parse_ref_general(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                              int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart,
+                              const int64_t *d_cline0, const grid_md_opts *opts, int32_t *d_flags, int64_t nlines,
+                              uint8_t *d_kept_line, void *d_keys_line, void *d_K, int32_t *d_kidx, int64_t *h_nK);
+/* grid_md_parse_map_general: as grid_md_parse_map (same arguments), but within a file the value of
+ * a key is that of the LAST line in file order that passes every filter.  Two launches over the
+ * same text, in stream order, no memory beyond d_Q (whose cells of these files must hold
+ * GRID_MISSING on entry): the tag pass leaves in each cell the largest line number of its kept
+ * lines, as the tag GRID_MISSING + 1 + line (atomic max; negative and above GRID_MISSING, never a
+ * depth, which is > 0); the resolve pass stores a line's depth iff the cell holds that line's tag
+ * and only then adds 1 to d_kept[f].  Afterwards no tag remains and d_kept[f] = the present cells
+ * of row f, whatever order the atomics arrived in.  A kept line past line 2^31 - 4 of its file has
+ * no tag: flags |= GRID_MD_LINES (the caller then uses the host parser). */
+#define GRID_MD_LINES 4    /* general keys: a file of more than 2^31 - 3 lines */
+int grid_md_parse_map_general(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                              int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart,
+                              const int64_t *d_cline0, const grid_md_opts *opts, int32_t *d_flags, const void *d_K,
+                              int64_t nK, const int32_t *d_kidx, int64_t ref_nlines, int32_t *d_Q, int64_t ldq,
+                              const int32_t *d_qrow, uint64_t *d_kept, const int32_t *d_fstatus);
 /* d_fstatus (may be NULL in grid_md_count / grid_md_parse_map: every file parsed) = per batch
  * file, nonzero when any of its inflate units failed (the file is dropped, as the reference
  * drops a sample whose gzip does not read): grid_file_status folds the units' statuses of a
