@@ -116,7 +116,7 @@ struct Inflater {
       p.wr(co + l, (uint16_t)(p.rd(co + l) + 1));
     }
     p.wr(co, 0);
-    int left = 1;                      // over-subscription check (incomplete codes allowed, as zlib)
+    int left = 1;                      // over-subscription check (dynamic_tables: legal_set() for incomplete sets)
     for (int l = 1; l < 16; l++) {
       left <<= 1;
       left -= p.rd(co + l);
@@ -146,6 +146,18 @@ struct Inflater {
       code <<= 1;
     }
     return true;
+  }
+
+  // zlib's rule for a block's own code sets (inflate_table), after build()
+  // has refused the over-subscribed ones: an incomplete set is an error too,
+  // unless it is a literal/length or distance set with no code at all or with
+  // a single code of length 1; the code-length code must be complete.  count[]
+  // at tab[co]; what the codes leave of the code space, in units of 2^-15
+  IC_HD bool legal_set(int co, bool may_lack) {
+    int left = 1 << 15;
+    for (int l = 1; l < 16; l++) left -= (int)p.rd(co + l) << (15 - l);
+    if (left == 0) return true;
+    return may_lack && (left == 1 << 15 || (left == 1 << 14 && p.rd(co + 1) == 1));
   }
 
   // slow decode (codes longer than the fast table, or any code): puff's walk
@@ -191,7 +203,7 @@ struct Inflater {
     if (nlen > 286 || ndist > 30) return false;
     for (int i = 0; i < 19; i++) p.wr(T_LENS + kClOrder[i], i < ncode ? (uint16_t)bits(3) : 0);
     // code-length code: its fast table is the distance one (DFAST >= 7)
-    if (!build(T_LENS, 19, 7, FT_DIST, T_CCNT, T_CSYM)) return false;
+    if (!build(T_LENS, 19, 7, FT_DIST, T_CCNT, T_CSYM) || !legal_set(T_CCNT, false)) return false;
     int idx = 0;
     while (idx < nlen + ndist) {
       const int sym = decode(FT_DIST, 7, T_CCNT, T_CSYM);
@@ -216,9 +228,9 @@ struct Inflater {
       idx += rep;
     }
     if (p.rd(T_LENS + 256) == 0) return false;   // no end-of-block code
-    if (!build(T_LENS, nlen, LFAST, FT_LEN, T_LCNT, T_LSYM)) return false;
+    if (!build(T_LENS, nlen, LFAST, FT_LEN, T_LCNT, T_LSYM) || !legal_set(T_LCNT, true)) return false;
     // the distance lengths follow the literal/length ones in the same slots
-    return build(T_LENS + nlen, ndist, DFAST, FT_DIST, T_DCNT, T_DSYM);
+    return build(T_LENS + nlen, ndist, DFAST, FT_DIST, T_DCNT, T_DSYM) && legal_set(T_DCNT, true);
   }
 
   IC_HD bool codes() {

@@ -1,7 +1,13 @@
 """gzip inflate on the device (grid_gunzip_batch; grid_amd/csrc/inflate.hip)
 against zlib: every DEFLATE block type and strategy, levels 0-9, multi-member
 and BGZF files, the golden cohorts' mosdepth files, empty text; corrupt and
-truncated files must be rejected exactly when zlib rejects them."""
+truncated files must be rejected exactly when zlib rejects them.  The
+compressor's streams cannot aim at the kernel's own constants (the 2 KiB LDS
+ring, its near/far copy boundary at RING - 258, the 1 KiB flushes, the fast
+tables, the last 296 bytes of output room and 16 bytes of input):
+test_hand_built_cases runs the hand-built streams of tests/inflate_cases.py,
+which do, through both launches, and checks that no byte outside a stream's
+own output is written."""
 import gzip
 import os
 import random
@@ -12,6 +18,7 @@ import numpy as np
 import pytest
 
 from grid_amd import _abi
+from tests import inflate_cases as ic
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -22,12 +29,16 @@ def _variants():
     texts = [b"", b"a", b"hello hello hello hello", bytes(rng.getrandbits(8) for _ in range(70000)),
              b"".join(b"chr1\t%d\t%d\t%.2f\n" % (i * 1000, i * 1000 + 1000, rng.uniform(0, 100)) for i in range(20000)),
              b"A" * 100000, bytes(range(256)) * 300]
-    # matches beyond the LDS ring (inflate.hip: dist > 8192 - 258 reads the
-    # flushed output in HBM), up to DEFLATE's 32768, and both sides of the edge
+    # matches beyond the LDS ring (inflate.hip: dist > NEAR = RING - 258 reads
+    # the flushed output in HBM), up to DEFLATE's 32768, and both sides of the
+    # edge and of the ring's size; 7933..8193 were the edges of the 8 KiB ring
     rb = lambda k: bytes(rng.getrandbits(8) for _ in range(k))    # noqa: E731
     x, y, a, b = rb(12000), rb(5000), rb(16384), rb(16384)
     texts += [x + y + x, a + b + a]
     for e in (7933, 7934, 7935, 7936, 8192, 8193):
+        z = rb(e)
+        texts.append(z + z + z[:300])
+    for e in (ic.NEAR - 1, ic.NEAR, ic.NEAR + 1, ic.RING - 1, ic.RING, ic.RING + 1):
         z = rb(e)
         texts.append(z + z + z[:300])
     out = []
@@ -183,3 +194,70 @@ def test_streams_at_any_offset(dev, mcap):
             assert st[f] != 0
         else:
             assert st[f] == 0 and bytes(host[out_off[f]:out_off[f] + ln[f]]) == r, f
+
+
+PATTERN = 0xA5
+
+
+@pytest.fixture(scope="module")
+def case_texts():
+    return {name: _zlib(blob) for name, blob, _ in ic.CASES}
+
+
+@pytest.mark.parametrize("mcap", [4, 1])
+def test_hand_built_cases(dev, case_texts, mcap):
+    """tests/inflate_cases.py through grid_gunzip_batch: file-granular (mcap =
+    4, k_gz_crc) and member-granular (mcap = 1, k_member_check: the
+    single-member cases).  Status zero and zlib's text where zlib accepts,
+    nonzero where it rejects, GZ_ECRC for a flipped trailer CRC, GZ_ESPACE one
+    byte short of room; every case at each of its capacities, the input-tail
+    family at input skews 0..3 (the others at one, varying), the output of
+    stream i 16-byte aligned or odd (the two launches swap); the output buffer
+    is pre-filled, and every byte outside an accepted stream's text or a
+    rejected stream's capacity must be untouched."""
+    streams = []                                   # (name, blob, expect, cap, skew)
+    for name, blob, expect in ic.CASES:
+        if ic.MEMBERS[name] > mcap:
+            continue
+        for extra in ic.CAP_EXTRA[name]:
+            skews = range(4) if ic.family(name) == "f09_tail" else [(len(streams) + mcap) & 3]
+            for skew in skews:
+                want = "space" if extra < 0 else "crc" if name in ic.CRC_FLIPPED else expect
+                streams.append((name, blob, want, ic.SIZE[name] + extra, skew))
+    n = len(streams)
+    src, in_off, out_off, opos = bytearray(), [], [], 0
+    for i, (name, blob, want, cap, skew) in enumerate(streams):
+        src += b"\xff" * ((skew - len(src)) % 4 + 4)
+        in_off.append(len(src))
+        src += blob
+        opos = -(-(opos + 32) // 16) * 16 + (0 if (i + mcap) % 2 == 0 else 1 + 2 * (i % 7))
+        out_off.append(opos)
+        opos += cap
+    assert all(o % 4 == s[4] for o, s in zip(in_off, streams))
+    total = opos + 256
+    d_src = dev.upload(np.frombuffer(bytes(src) + b"\x00" * 256, np.uint8))
+    d_io, d_il = dev.upload(np.array(in_off, np.int64)), dev.upload(np.array([len(s[1]) for s in streams], np.int64))
+    d_oo, d_cap = dev.upload(np.array(out_off, np.int64)), dev.upload(np.array([s[3] for s in streams], np.int64))
+    out = dev.alloc(total, np.uint8).fill_bytes(PATTERN)
+    mem = dev.alloc(n * mcap * _abi.GZ_MEMBER_BYTES, np.uint8)
+    st, ln, nm = dev.alloc(n, np.int32), dev.alloc(n, np.int64), dev.alloc(n, np.int32)
+    _abi.call("grid_gunzip_batch", dev.ctx, d_src.ptr, d_io.ptr, d_il.ptr, n, out.ptr, d_oo.ptr, d_cap.ptr, mem.ptr,
+              mcap, st.ptr, ln.ptr, nm.ptr)
+    st, ln, host = st.numpy(), ln.numpy(), out.numpy()
+    own = np.zeros(total, bool)                    # bytes a stream may have written
+    bad = []
+    for f, (name, blob, want, cap, skew) in enumerate(streams):
+        o = out_off[f]
+        if want == "ok":
+            t = case_texts[name]
+            own[o:o + len(t)] = True
+            if st[f] != 0 or ln[f] != len(t) or bytes(host[o:o + len(t)]) != t:
+                bad.append((name, cap, skew, int(st[f]), int(ln[f])))
+        else:
+            own[o:o + cap] = True
+            code = {"space": _abi.GZ_ESPACE, "crc": _abi.GZ_ECRC}.get(want)
+            if st[f] == 0 or (code is not None and st[f] != code):
+                bad.append((name, cap, skew, int(st[f]), int(ln[f])))
+    assert not bad, bad[:20]
+    touched = np.flatnonzero(~own & (host != PATTERN))
+    assert touched.size == 0, [(int(t), streams[int(np.searchsorted(out_off, t, "right")) - 1][0]) for t in touched[:10]]

@@ -6,43 +6,25 @@ fixed and dynamic blocks, codes up to 15 bits (the canonical walk), matches up
 to 32 KiB back, multi-member (BGZF) streams, and truncated / corrupt input.
 The device's own fast loop is covered against zlib on the GPU
 (tests/test_gpu_inflate.py)."""
-import ctypes as C
 import gzip
-import os
 import shutil
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import inflate_cases
 
 
 @pytest.fixture(scope="module", params=[8, 10])
 def core(request, tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("g++ not present")
-    d = tmp_path_factory.mktemp(f"icore{request.param}")
-    so = d / "libicore.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-DGRID_INFLATE_LFAST={request.param}",
-                    "-I" + os.path.join(ROOT, "grid_amd", "csrc"), os.path.join(ROOT, "tests", "native",
-                                                                                "inflate_core_host.cpp"),
-                    "-o", str(so), "-lz"], check=True)
-    lib = C.CDLL(str(so))
-    lib.host_gunzip.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
-                                C.POINTER(C.c_int32)]
-    assert lib.host_lfast() == request.param
-    return lib
+    return inflate_cases.host_core(request.param, tmp_path_factory.mktemp(f"icore{request.param}"))
 
 
-def run(lib, blob, cap):
-    src = np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)
-    out = np.zeros(max(cap, 1), np.uint8)
-    n, m = C.c_int64(), C.c_int32()
-    rc = lib.host_gunzip(src.ctypes.data, len(blob), out.ctypes.data, cap, C.byref(n), C.byref(m))
-    return rc, out[: n.value].tobytes(), m.value
+run = inflate_cases.host_gunzip
 
 
 def bgzf(data, block=65280, level=6):
