@@ -149,10 +149,10 @@ __device__ __forceinline__ void rb_finish_plain(const T *s_q, double *s_leaf, in
 // 64 leaves x 8 chains = 512 chains, 2 per thread; leaf results combined in
 // the fixed binary tree of pairwise(8192).
 // SRC: 0 = int32 (int4 loads), 1 = int32 (scalar loads), 3 = int32 (streaming / nontemporal int4 loads; GRID_ROWBLK_NT A/B)
-// XOR: blocks without a missing cell (found by a minimum: GRID_MISSING is
+// Blocks without a missing cell (found by a minimum: GRID_MISSING is
 // INT32_MIN) take rb_finish_plain; the others count their cells from LDS.
 constexpr bool ROWBLK_NT = true;   // default for GRID_ROWBLK_NT
-template <int SRC, bool XOR = true>
+template <int SRC>
 __global__ __launch_bounds__(256) void k_row_blocks_full(const int32_t *__restrict__ q, Q16 s16, int64_t ld,
                                                          int64_t nblk_full, int64_t nblk,
                                                          double *__restrict__ bsum,
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_row_blocks_full(const int32_t *__restri
   const int64_t b = blockIdx.x;
   const int64_t row = blockIdx.y;
   const int tid = threadIdx.x;
-  int cnt = 0, mn = 0;
+  int mn = 0;
   {
     const int32_t *srcp = q + row * ld + b * BLK;
     const int4 *src = reinterpret_cast<const int4 *>(srcp);
@@ -183,33 +183,30 @@ __global__ __launch_bounds__(256) void k_row_blocks_full(const int32_t *__restri
       int e = e4 * 4;
       int leaf = e >> 7, w = e & 127;
       *reinterpret_cast<int4 *>(&s_q[leaf * LEAF_PAD + w]) = v;
-      if constexpr (XOR) mn = min(mn, min(min(v.x, v.y), min(v.z, v.w)));
-      else cnt += (v.x != GRID_MISSING) + (v.y != GRID_MISSING) + (v.z != GRID_MISSING) + (v.w != GRID_MISSING);
+      mn = min(mn, min(min(v.x, v.y), min(v.z, v.w)));
     }
   }
-  if constexpr (XOR) {
-    // workgroup-uniform branch (readfirstlane of the barrier's OR, see k_row_blocks16)
-    if (__builtin_expect(!__builtin_amdgcn_readfirstlane(__syncthreads_or(mn == GRID_MISSING)), 1)) {
-      rb_finish_plain(s_q, s_leaf, row, b, nblk, bsum, bcnt);
-      return;
-    }
+  // workgroup-uniform branch (readfirstlane of the barrier's OR, see k_row_blocks16)
+  if (__builtin_expect(!__builtin_amdgcn_readfirstlane(__syncthreads_or(mn == GRID_MISSING)), 1)) {
+    rb_finish_plain(s_q, s_leaf, row, b, nblk, bsum, bcnt);
+    return;
+  }
+  int cnt = 0;
 #pragma unroll
-    for (int it = 0; it < 8; it++) {
-      const int e = (it * 256 + tid) * 4;
-      const int4 v = *reinterpret_cast<const int4 *>(&s_q[(e >> 7) * LEAF_PAD + (e & 127)]);
-      cnt += (v.x != GRID_MISSING) + (v.y != GRID_MISSING) + (v.z != GRID_MISSING) + (v.w != GRID_MISSING);
-    }
+  for (int it = 0; it < 8; it++) {
+    const int e = (it * 256 + tid) * 4;
+    const int4 v = *reinterpret_cast<const int4 *>(&s_q[(e >> 7) * LEAF_PAD + (e & 127)]);
+    cnt += (v.x != GRID_MISSING) + (v.y != GRID_MISSING) + (v.z != GRID_MISSING) + (v.w != GRID_MISSING);
   }
   rb_finish(s_q, [](int32_t v, int) { return qval(v); }, s_leaf, s_cnt, cnt, row, b, nblk, bsum, bcnt);
 }
 
-// ---- compact codes: PB consecutive full blocks per workgroup ----
+// ---- compact codes: one full block per workgroup ----
 // The codes stay uint16 in LDS (17 KiB per block image instead of 35 KiB of
 // decoded int32: twice the resident workgroups, so one workgroup's loads
 // overlap another's chain sums) and are decoded where the chains read them;
-// an escape (rare) is looked up out of line.  PB blocks' codes are loaded up
-// front (PB x 4 uint4 per thread).
-constexpr int RB16_PB = 1;   // default for GRID_ROWBLK16_PB (timing only)
+// an escape (rare) is looked up out of line.  The block's codes are loaded up
+// front (4 uint4 per thread).
 typedef unsigned rb_v4u __attribute__((ext_vector_type(4)));
 
 template <bool NT>
@@ -224,7 +221,6 @@ __device__ __forceinline__ void rb16_load(const Q16 &s16, int64_t ld, int64_t ro
 
 // One full block (row, b) from its codes in registers: LDS image, then the
 // chains and tree of rb_finish.  Ends with every LDS read done.
-template <bool RB16_XOR>
 __device__ __forceinline__ void rb16_block(const rb_v4u (&raw)[4], const Q16 &s16, int64_t row, int64_t b,
                                            int64_t nblk, uint16_t *s_q, double *s_leaf, int *s_cnt,
                                            double *__restrict__ bsum, int32_t *__restrict__ bcnt) {
@@ -252,12 +248,7 @@ __device__ __forceinline__ void rb16_block(const rb_v4u (&raw)[4], const Q16 &s1
   // readfirstlane makes the branch scalar, so no wave can skip the
   // barriers of either side (tools/isa_barriers.py)
   if (__builtin_expect(!__builtin_amdgcn_readfirstlane(__syncthreads_or(special)), 1)) {
-    if constexpr (RB16_XOR) {
-      rb_finish_plain(s_q, s_leaf, row, b, nblk, bsum, bcnt);
-    } else {
-      rb_finish(s_q, [](uint16_t c, int) { return div100_exact((int32_t)c); }, s_leaf, s_cnt, BLK / 256, row, b,
-                nblk, bsum, bcnt);
-    }
+    rb_finish_plain(s_q, s_leaf, row, b, nblk, bsum, bcnt);
   } else {
     int cnt = 0;
 #pragma unroll
@@ -273,56 +264,28 @@ __device__ __forceinline__ void rb16_block(const rb_v4u (&raw)[4], const Q16 &s1
   }
 }
 
-template <int PB, bool NT, bool XOR = true>
+template <bool NT>
 __global__ __launch_bounds__(256) void k_row_blocks16(Q16 s16, int64_t ld, int64_t nblk_full, int64_t nblk,
                                                       double *__restrict__ bsum, int32_t *__restrict__ bcnt) {
   __shared__ __attribute__((aligned(16))) uint16_t s_q[64 * LEAF_PAD];
   __shared__ double s_leaf[64];
   __shared__ int s_cnt[4];
-  const int64_t row = blockIdx.y, b0 = (int64_t)blockIdx.x * PB;
-  rb_v4u raw[PB][4];
+  const int64_t row = blockIdx.y, b = blockIdx.x;
+  rb_v4u raw[4];
+  // The grid has nblk_full workgroups per row, so b < nblk_full always holds.
+  // The test and the one-trip loop are what is left of the form that took
+  // several blocks per workgroup; written so, the kernel compiles to the same
+  // machine code as that form did at one block (an early return does not).
+  if (b < nblk_full) rb16_load<NT>(s16, ld, row, b, raw);
 #pragma unroll
-  for (int h = 0; h < PB; h++)
-    if (b0 + h < nblk_full) rb16_load<NT>(s16, ld, row, b0 + h, raw[h]);
-#pragma unroll
-  for (int h = 0; h < PB; h++) {
-    const int64_t b = b0 + h;
+  for (int h = 0; h < 1; h++) {
     if (b >= nblk_full) break;                      // workgroup-uniform
-    if (h > 0) __syncthreads();                     // the previous block's LDS reads are done
-    rb16_block<XOR>(raw[h], s16, row, b, nblk, s_q, s_leaf, s_cnt, bsum, bcnt);
-  }
-}
-
-// Streamed form (GRID_ROWBLK16_PB=0): a grid of resident workgroups walks the
-// (row, block) units u = blockIdx.x, + gridDim.x, ... (row-major, so the
-// workgroups in flight read neighbouring blocks of a row), holding the next
-// unit's codes in registers while this one is summed: the loads of one unit
-// overlap the chains of the previous one inside every workgroup, instead of
-// a workgroup per unit that waits for its loads before any work.
-template <bool NT, bool XOR = true>
-__global__ __launch_bounds__(256) void k_row_blocks16s(Q16 s16, int64_t ld, int64_t n, int64_t nblk_full,
-                                                       int64_t nblk, double *__restrict__ bsum,
-                                                       int32_t *__restrict__ bcnt) {
-  __shared__ __attribute__((aligned(16))) uint16_t s_q[64 * LEAF_PAD];
-  __shared__ double s_leaf[64];
-  __shared__ int s_cnt[4];
-  const int64_t total = n * nblk_full, step = gridDim.x;
-  int64_t u = blockIdx.x;
-  if (u >= total) return;                           // workgroup-uniform
-  rb_v4u cur[4], nxt[4];
-  rb16_load<NT>(s16, ld, u / nblk_full, u % nblk_full, cur);
-  for (; u < total; u += step) {
-    const int64_t un = u + step;
-    if (un < total) rb16_load<NT>(s16, ld, un / nblk_full, un % nblk_full, nxt);
-    rb16_block<XOR>(cur, s16, u / nblk_full, u % nblk_full, nblk, s_q, s_leaf, s_cnt, bsum, bcnt);
-    __syncthreads();                                // this unit's LDS reads are done before the next image
-#pragma unroll
-    for (int it = 0; it < 4; it++) cur[it] = nxt[it];
+    rb16_block(raw, s16, row, b, nblk, s_q, s_leaf, s_cnt, bsum, bcnt);
   }
 }
 
 // ---- generic pairwise_sum (numpy) for a partial block, one thread ----
-// G: element accessor, get(k) -> int32 hundredths of element k.
+// V: element accessor, val(k) -> the value of element k.
 template <class V>
 __device__ double pairwise_leaf_v(const V &val, int lo, int n) {
   auto a = [&](int i) { return val(lo + i); };
@@ -344,10 +307,6 @@ __device__ double pairwise_leaf_v(const V &val, int lo, int n) {
   double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
   for (; i < n; i++) res = res + a(i);
   return res;
-}
-template <class G>
-__device__ double pairwise_leaf(const G &get, int lo, int n) {
-  return pairwise_leaf_v([&](int k) { return qval(get(k)); }, lo, n);
 }
 
 // numpy's recursion over [0, n) with the leaves supplied by leaf(lo, len) in
@@ -385,53 +344,13 @@ __device__ double pairwise_tree(int n, const L &leaf) {
   return ret;
 }
 
-// The partial last block of every row, one wave per row: lane 0 lists the
-// recursion's leaves (<= 128 for a block < 8192), the lanes sum the leaves in
-// parallel (each leaf exactly as pairwise_leaf), lane 0 combines them in the
-// recursion's order (NumPy's pairwise_sum).  ~0.47 ms -> tens of us at the
-// bench shape (one thread per row walked 1,728 elements serially).
-template <bool S16>
-__global__ __launch_bounds__(64) void k_row_block_tail_w(const int32_t *__restrict__ q, Q16 s16, int64_t ld,
-                                                          int64_t m, int64_t nblk, double *__restrict__ bsum,
-                                                          int32_t *__restrict__ bcnt) {
-  __shared__ int s_lo[128], s_len[128];
-  __shared__ double s_val[128];
-  __shared__ int s_nl;
-  const int64_t row = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int64_t b = nblk - 1;
-  const int len = (int)(m - b * BLK);
-  const int64_t c0 = b * BLK;
-  auto get = [&](int k) -> int32_t {
-    if constexpr (S16) return q16_val(s16.q[row * ld + c0 + k], row, c0 + k, s16);
-    else return q[row * ld + c0 + k];
-  };
-  if (lane == 0) {
-    int nl = 0;
-    pairwise_tree(len, [&](int lo, int nn) { s_lo[nl] = lo; s_len[nl] = nn; nl++; return 0.0; });
-    s_nl = nl;
-  }
-  int c = 0;
-  for (int i = lane; i < len; i += 64) c += get(i) != GRID_MISSING;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-  __syncthreads();
-  for (int l = lane; l < s_nl; l += 64) s_val[l] = pairwise_leaf(get, s_lo[l], s_len[l]);
-  __syncthreads();
-  if (lane == 0) {
-    int k = 0;
-    bsum[row * nblk + b] = pairwise_tree(len, [&](int, int) { return s_val[k++]; });
-    bcnt[row * nblk + b] = c;
-  }
-}
-
-
 // The partial last block with its pairwise tree planned on the host (the tail
 // length is the same for every row, so is numpy's recursion): leaves in
 // left-to-right order, internal nodes grouped by height, each the sum of two
 // earlier values.  One wave per row stages the tail in LDS with 16-B loads,
-// sums one leaf per lane (pairwise_leaf's order) and evaluates the tree a
-// height at a time.  k_row_block_tail_w walked the recursion on lane 0 with
-// its stack in scratch: 537 us at 375,000 bins (6,360-element tails).
+// sums one leaf per lane (pairwise_leaf_v's order) and evaluates the tree a
+// height at a time.  (Walking the recursion on lane 0, its stack in scratch,
+// took 537 us at 375,000 bins, 6,360-element tails.)
 constexpr int TP_MAXL = 128, TP_MAXH = 10;
 struct TailPlan {
   int32_t nleaf, nnode, nh;
@@ -552,107 +471,73 @@ __global__ void k_recip(const double *__restrict__ v, int64_t n, double *__restr
 
 constexpr int CU = 8;   // rows unrolled per iteration in the column kernels
 
-// VW adjacent columns per thread, sequential over rows: int4 loads of int32
-// (VW == 4), or one 8-B load of 4 compact uint16 values (S16).
+// The column kernels walk the rows in order, one thread per COL_VW adjacent
+// columns.  Two forms:
+//  * int32 matrix: 1 column per thread (47 k waves at the bench shape, ~6
+//    rounds of resident waves; 4 per thread left a 2.3-round tail: 14.5 vs
+//    13.7 ms), plain or streaming (nontemporal) loads (NTL, GRID_COL_NT);
+//  * compact codes: 2 columns per thread (one 4-byte streaming load per row),
+//    software-pipelined row groups (below).
 constexpr bool COL_NT = true;   // default for GRID_COL_NT
-constexpr int COL16_VW = 2;     // default for GRID_COL16_VW (compact codes)
-constexpr bool COL_PF = true;   // default for GRID_COL_PF (r04o: 10.77 -> 10.67 ms at config 2, 1.63 -> 1.43 at 1/8 bins)
-// CHECK = false (compact codes): the raw codes only, so a group of rows can
-// be loaded before any value is inspected; fix16() then decodes the group.
-template <int VW, bool S16, bool NTL = false, bool CHECK = true>
+template <bool S16>
+constexpr int COL_VW = S16 ? 2 : 1;
+
+// One row of a thread's columns, decoded (compact codes: missing cells and
+// escapes looked up).
+template <bool S16, bool NTL>
 __device__ __forceinline__ void load_row(const int32_t *__restrict__ q, const Q16 &s16, int64_t i, int64_t ld,
-                                         int64_t j0, int32_t (&v)[VW]) {
+                                         int64_t j0, int32_t (&v)[COL_VW<S16>]) {
   if constexpr (S16) {
-    // 2 (VW 1), 4 (VW 2), 8 (VW 4) or 16 (VW 8) bytes of uint16 codes per row
-    static_assert(VW == 1 || VW == 2 || VW == 4 || VW == 8, "compact rows load 1, 2, 4 or 8 columns");
-    const uint16_t *p = s16.q + i * ld + j0;
-    if constexpr (VW == 8) {
-      typedef unsigned v4u __attribute__((ext_vector_type(4)));
-      const v4u u = NTL ? __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p))
-                        : *reinterpret_cast<const v4u *>(p);
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        v[2 * k] = (int32_t)(u[k] & 0xFFFFu);
-        v[2 * k + 1] = (int32_t)(u[k] >> 16);
-      }
-    } else if constexpr (VW == 4) {
-      const uint2 u = *reinterpret_cast<const uint2 *>(p);
-      v[0] = (int32_t)(u.x & 0xFFFFu); v[1] = (int32_t)(u.x >> 16);
-      v[2] = (int32_t)(u.y & 0xFFFFu); v[3] = (int32_t)(u.y >> 16);
-    } else if constexpr (VW == 2) {
-      const uint32_t u = NTL ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p))
-                             : *reinterpret_cast<const uint32_t *>(p);
-      v[0] = (int32_t)(u & 0xFFFFu); v[1] = (int32_t)(u >> 16);
-    } else {
-      v[0] = (int32_t)(NTL ? __builtin_nontemporal_load(p) : *p);
-    }
-    if constexpr (!CHECK) return;
+    const uint32_t u = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(s16.q + i * ld + j0));
+    v[0] = (int32_t)(u & 0xFFFFu); v[1] = (int32_t)(u >> 16);
     // rare: missing cells and escapes (one out-of-line call, not per element)
-    int32_t mx = v[0];
+    if (__builtin_expect(max(v[0], v[1]) > GRID_Q16_MAXV, 0)) {
 #pragma unroll
-    for (int k = 1; k < VW; k++) mx = max(mx, v[k]);
-    if (__builtin_expect(mx > GRID_Q16_MAXV, 0)) {
-#pragma unroll
-      for (int k = 0; k < VW; k++)
+      for (int k = 0; k < 2; k++)
         if (v[k] > GRID_Q16_MAXV) v[k] = q16_slow((uint32_t)v[k], i, j0 + k, s16);
     }
-  } else if constexpr (VW == 4) {
-    int4 t = *reinterpret_cast<const int4 *>(q + i * ld + j0);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else if constexpr (VW == 2) {
-    int2 t = *reinterpret_cast<const int2 *>(q + i * ld + j0);
-    v[0] = t.x; v[1] = t.y;
   } else {
-#pragma unroll
-    for (int c = 0; c < VW; c++) {
-      if constexpr (NTL) v[c] = __builtin_nontemporal_load(q + i * ld + j0 + c);   // streamed once
-      else v[c] = q[i * ld + j0 + c];
-    }
+    if constexpr (NTL) v[0] = __builtin_nontemporal_load(q + i * ld + j0);   // streamed once
+    else v[0] = q[i * ld + j0];
   }
 }
-// Decode a group of CUN rows of raw compact codes (missing -> GRID_MISSING,
+// Decode a group of CU rows of raw compact codes (missing -> GRID_MISSING,
 // escapes looked up); one test of the group's largest code on the fast path.
-template <int CUN, int VW>
-__device__ __forceinline__ void fix16(int32_t (&v)[CUN][VW], int64_t i, int64_t j0, const Q16 &s16) {
+__device__ __forceinline__ void fix16(int32_t (&v)[CU][2], int64_t i, int64_t j0, const Q16 &s16) {
   int32_t mx = v[0][0];
 #pragma unroll
-  for (int u = 0; u < CUN; u++)
+  for (int u = 0; u < CU; u++)
 #pragma unroll
-    for (int c = 0; c < VW; c++) mx = max(mx, v[u][c]);
+    for (int c = 0; c < 2; c++) mx = max(mx, v[u][c]);
   if (__builtin_expect(mx > GRID_Q16_MAXV, 0)) {
 #pragma unroll
-    for (int u = 0; u < CUN; u++)
+    for (int u = 0; u < CU; u++)
 #pragma unroll
-      for (int c = 0; c < VW; c++)
+      for (int c = 0; c < 2; c++)
         if (v[u][c] > GRID_Q16_MAXV)
           v[u][c] = v[u][c] == GRID_Q16_MISS ? GRID_MISSING : q16_lookup(i + u, j0 + c, s16);
   }
 }
 
-// True when every cell of a group of CUN rows is an ordinary depth: no
+// True when every cell of a group of CU rows is an ordinary depth: no
 // missing cell / escape code and every row mean nonzero and not NaN (rm is
 // the same for all lanes: scalar loads).  Such a group needs no per-cell
 // masks: missing cells and zero rows are rare and take the masked path.
-template <bool S16, int CUN, int VW>
-__device__ __forceinline__ bool plain_group(const int32_t (&v)[CUN][VW], const uint8_t *__restrict__ badg) {
-  static_assert(CUN % 8 == 0, "row groups of whole 8-byte flag words");
-  uint64_t bad = 0;                                   // k_recip's row flags, 8 per load (i % 8 == 0)
-#pragma unroll
-  for (int u = 0; u < CUN; u += 8) bad |= *reinterpret_cast<const uint64_t *>(badg + u);
-  const bool rows = bad == 0;
+template <bool S16>
+__device__ __forceinline__ bool plain_group(const int32_t (&v)[CU][COL_VW<S16>], const uint8_t *__restrict__ badg) {
+  static_assert(CU == 8, "a row group is one 8-byte word of k_recip's row flags (i % 8 == 0)");
+  const bool rows = *reinterpret_cast<const uint64_t *>(badg) == 0;
   if constexpr (S16) {
     int32_t mx = v[0][0];
 #pragma unroll
-    for (int u = 0; u < CUN; u++)
+    for (int u = 0; u < CU; u++)
 #pragma unroll
-      for (int c = 0; c < VW; c++) mx = max(mx, v[u][c]);
+      for (int c = 0; c < 2; c++) mx = max(mx, v[u][c]);
     return rows && mx <= GRID_Q16_MAXV;
   } else {
     int32_t mn = v[0][0];
 #pragma unroll
-    for (int u = 0; u < CUN; u++)
-#pragma unroll
-      for (int c = 0; c < VW; c++) mn = min(mn, v[u][c]);
+    for (int u = 0; u < CU; u++) mn = min(mn, v[u][0]);
     return rows && mn != GRID_MISSING;
   }
 }
@@ -664,50 +549,42 @@ __device__ __forceinline__ int32_t q_at(const int32_t *__restrict__ q, const Q16
   else return q[i * ld + j];
 }
 
-// Raw compact codes of CUN rows: one 2-byte code (VW 1) or 2 codes (columns
-// j0, j0 + 1) per 4-byte word (VW 2), one register per row either way.
-template <int VW, int CUN, bool NTL>
-__device__ __forceinline__ void ld_raw(const Q16 &s16, int64_t i0, int64_t ld, int64_t j0, uint32_t (&w)[CUN]) {
-  static_assert(VW == 1 || VW == 2, "raw rows of 1 or 2 compact codes");
+// Raw compact codes of CU rows: columns j0, j0 + 1 in one 4-byte word, one
+// register per row.
+__device__ __forceinline__ void ld_raw(const Q16 &s16, int64_t i0, int64_t ld, int64_t j0, uint32_t (&w)[CU]) {
 #pragma unroll
-  for (int u = 0; u < CUN; u++) {
-    const uint16_t *p16 = s16.q + (i0 + u) * ld + j0;
-    if constexpr (VW == 2) {
-      const uint32_t *p = reinterpret_cast<const uint32_t *>(p16);
-      w[u] = NTL ? __builtin_nontemporal_load(p) : *p;
-    } else {
-      w[u] = NTL ? __builtin_nontemporal_load(p16) : *p16;
-    }
-  }
+  for (int u = 0; u < CU; u++)
+    w[u] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(s16.q + (i0 + u) * ld + j0));
 }
-template <int VW, int CUN>
-__device__ __forceinline__ void unpack_raw(const uint32_t (&w)[CUN], int32_t (&v)[CUN][VW]) {
+__device__ __forceinline__ void unpack_raw(const uint32_t (&w)[CU], int32_t (&v)[CU][2]) {
 #pragma unroll
-  for (int u = 0; u < CUN; u++) {
+  for (int u = 0; u < CU; u++) {
     v[u][0] = (int32_t)(w[u] & 0xFFFFu);
-    if constexpr (VW == 2) v[u][1] = (int32_t)(w[u] >> 16);
+    v[u][1] = (int32_t)(w[u] >> 16);
   }
 }
 
-// PF: software-pipelined row groups (the next group's loads issued before
-// this group is summed; the summation order is unchanged).
+// Compact codes: software-pipelined row groups (the next PFD groups' loads
+// issued before this group is summed; the summation order is unchanged).
 // WPE: waves per SIMD the register budget is held to.  A thread walks all n
 // rows of its columns, so a launch runs in ROUNDS of resident waves: the
 // compact pipelined kernel took 68 VGPRs (7 waves per SIMD, 7,168 on the chip),
 // and config 2's 23,438 waves ran 3.27 rounds -- a fourth round a quarter full;
 // at 61 VGPRs (8 per SIMD, no spill) they run 2.86, i.e. 3 rounds.
-// PFD (compact pipelined path): row groups in flight ahead of the one being
+// PFD: row groups in flight ahead of the one being
 // summed -- 1 by default; a launch of less than one round of resident waves
 // (the per-rank shards of a multi-GPU run: 2,930 waves at 3,202 x 375,000)
 // takes 3, since each wave's serial walk over the rows is then latency-bound.
-template <int VW, bool S16, int CUN = CU, bool NTL = false, bool PF = false, int WPE = 1, int PFD = 1>
+// Instantiated as (WPE, PFD) = (8, 1) and (4, 3); the int32 form leaves both at 1.
+template <bool S16, bool NTL, int WPE = 1, int PFD = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_col_means(const int32_t *__restrict__ q, Q16 s16, int64_t n, int64_t m,
                                                    int64_t ld, const double *__restrict__ rm,
                                                    const double *__restrict__ rinv, const uint8_t *__restrict__ rbad,
                                                    double *__restrict__ mu) {
+  constexpr int VW = COL_VW<S16>;
   const int64_t j0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VW;
   if (j0 >= m) return;
-  if (VW > 1 && j0 + VW > m) {   // ragged tail: scalar path
+  if (VW > 1 && j0 + VW > m) {   // ragged tail (compact codes): scalar path
     for (int64_t j = j0; j < m; j++) {
       double acc = 0.0;
       int64_t c = 0;
@@ -723,26 +600,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
   int64_t cnt[VW];
 #pragma unroll
   for (int c = 0; c < VW; c++) { acc[c] = 0.0; cnt[c] = 0; }
-  auto ld_grp = [&](int32_t (&v)[CUN][VW], int64_t i0) {
+  auto ld_grp = [&](int32_t (&v)[CU][VW], int64_t i0) {
 #pragma unroll
-    for (int u = 0; u < CUN; u++) load_row<VW, S16, NTL, false>(q, s16, i0 + u, ld, j0, v[u]);
+    for (int u = 0; u < CU; u++) load_row<S16, NTL>(q, s16, i0 + u, ld, j0, v[u]);
   };
-  auto do_grp = [&](int32_t (&v)[CUN][VW], int64_t i) {
-    if (__builtin_expect(plain_group<S16, CUN, VW>(v, rbad + i), 1)) {
+  auto do_grp = [&](int32_t (&v)[CU][VW], int64_t i) {
+    if (__builtin_expect(plain_group<S16>(v, rbad + i), 1)) {
       // every cell valid (the common case): no per-cell masks or counts
 #pragma unroll
-      for (int u = 0; u < CUN; u++) {
+      for (int u = 0; u < CU; u++) {
         const double r = rm[i + u], ri = rinv[i + u];
 #pragma unroll
         for (int c = 0; c < VW; c++) acc[c] = acc[c] + div_exact(div100_exact(v[u][c]), r, ri);
       }
 #pragma unroll
-      for (int c = 0; c < VW; c++) cnt[c] += CUN;
+      for (int c = 0; c < VW; c++) cnt[c] += CU;
       return;
     }
-    if constexpr (S16) fix16<CUN, VW>(v, i, j0, s16);
+    if constexpr (S16) fix16(v, i, j0, s16);
 #pragma unroll
-    for (int u = 0; u < CUN; u++) {
+    for (int u = 0; u < CU; u++) {
       const double r = rm[i + u], ri = rinv[i + u];
 #pragma unroll
       for (int c = 0; c < VW; c++) {
@@ -751,51 +628,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
       }
     }
   };
-  const int64_t ng = n / CUN;
   int64_t i = 0;
-  if constexpr (PF && S16 && VW <= 2) {
+  if constexpr (S16) {
     // the next PFD groups' codes in flight while this group is summed (same
     // order), held as the raw 4-byte words (2 codes each): 8 registers per
     // group, so the pipelined loop (PFD 1) keeps the occupancy of the plain one
     constexpr int NB = PFD + 1;
-    uint32_t w[NB][CUN];
+    const int64_t ng = n / CU;
+    uint32_t w[NB][CU];
 #pragma unroll
     for (int b = 0; b < PFD; b++)
-      if (b < ng) ld_raw<VW, CUN, NTL>(s16, b * CUN, ld, j0, w[b]);
+      if (b < ng) ld_raw(s16, b * CU, ld, j0, w[b]);
     for (int64_t g = 0; g < ng; g += NB) {
 #pragma unroll
       for (int b = 0; b < NB; b++) {
         const int64_t gg = g + b;
         if (gg >= ng) break;
-        if (gg + PFD < ng) ld_raw<VW, CUN, NTL>(s16, (gg + PFD) * CUN, ld, j0, w[(b + PFD) % NB]);
-        int32_t v[CUN][VW];
-        unpack_raw<VW, CUN>(w[b], v);
-        do_grp(v, gg * CUN);
+        if (gg + PFD < ng) ld_raw(s16, (gg + PFD) * CU, ld, j0, w[(b + PFD) % NB]);
+        int32_t v[CU][VW];
+        unpack_raw(w[b], v);
+        do_grp(v, gg * CU);
       }
     }
-    i = ng * CUN;
-  } else if constexpr (PF) {
-    // the next group's loads are in flight while this group is summed (same order)
-    int32_t va[CUN][VW], vb[CUN][VW];
-    if (ng > 0) ld_grp(va, 0);
-    for (int64_t g = 0; g < ng; g += 2) {
-      if (g + 1 < ng) ld_grp(vb, (g + 1) * CUN);
-      do_grp(va, g * CUN);
-      if (g + 1 >= ng) break;
-      if (g + 2 < ng) ld_grp(va, (g + 2) * CUN);
-      do_grp(vb, (g + 1) * CUN);
-    }
-    i = ng * CUN;
+    i = ng * CU;
   } else {
-    for (; i + CUN <= n; i += CUN) {
-      int32_t v[CUN][VW];
+    for (; i + CU <= n; i += CU) {
+      int32_t v[CU][VW];
       ld_grp(v, i);
       do_grp(v, i);
     }
   }
   for (; i < n; i++) {
     int32_t v[VW];
-    load_row<VW, S16, NTL>(q, s16, i, ld, j0, v);
+    load_row<S16, NTL>(q, s16, i, ld, j0, v);
 #pragma unroll
     for (int c = 0; c < VW; c++) {
       double y;
@@ -806,16 +671,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
   for (int c = 0; c < VW; c++) mu[j0 + c] = acc[c] / (double)cnt[c];   // 0/0 -> NaN (numpy)
 }
 
-template <int VW, bool S16, int CUN = CU, bool NTL = false, bool PF = false, int WPE = 1, int PFD = 1>
+template <bool S16, bool NTL, int WPE = 1, int PFD = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_col_vars(const int32_t *__restrict__ q, Q16 s16, int64_t n, int64_t m,
                                                   int64_t ld, const double *__restrict__ rm,
                                                   const double *__restrict__ rinv, const uint8_t *__restrict__ rbad,
                                                   const double *__restrict__ mu, double *__restrict__ var,
                                                   double *__restrict__ ratio) {
+  constexpr int VW = COL_VW<S16>;
   const int64_t j0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VW;
   if (j0 >= m) return;
   const double qnan = __builtin_nan("");
-  if (VW > 1 && j0 + VW > m) {
+  if (VW > 1 && j0 + VW > m) {   // ragged tail (compact codes): scalar path
     for (int64_t j = j0; j < m; j++) {
       const double mj = mu[j];
       double acc = 0.0;
@@ -835,16 +701,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
   double acc[VW], mj[VW];
 #pragma unroll
   for (int c = 0; c < VW; c++) { acc[c] = 0.0; mj[c] = mu[j0 + c]; }
-  auto ld_grp = [&](int32_t (&v)[CUN][VW], int64_t i0) {
+  auto ld_grp = [&](int32_t (&v)[CU][VW], int64_t i0) {
 #pragma unroll
-    for (int u = 0; u < CUN; u++) load_row<VW, S16, NTL, false>(q, s16, i0 + u, ld, j0, v[u]);
+    for (int u = 0; u < CU; u++) load_row<S16, NTL>(q, s16, i0 + u, ld, j0, v[u]);
   };
-  auto do_grp = [&](int32_t (&v)[CUN][VW], int64_t i) {
-    if (__builtin_expect(plain_group<S16, CUN, VW>(v, rbad + i), 1)) {
+  auto do_grp = [&](int32_t (&v)[CU][VW], int64_t i) {
+    if (__builtin_expect(plain_group<S16>(v, rbad + i), 1)) {
       // every cell valid: y is finite, so dd is NaN only when mu_j is, and
       // then every term is (the sum is reset to nansum's 0 below)
 #pragma unroll
-      for (int u = 0; u < CUN; u++) {
+      for (int u = 0; u < CU; u++) {
         const double r = rm[i + u], ri = rinv[i + u];
 #pragma unroll
         for (int c = 0; c < VW; c++) {
@@ -854,9 +720,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
       }
       return;
     }
-    if constexpr (S16) fix16<CUN, VW>(v, i, j0, s16);
+    if constexpr (S16) fix16(v, i, j0, s16);
 #pragma unroll
-    for (int u = 0; u < CUN; u++) {
+    for (int u = 0; u < CU; u++) {
       const double r = rm[i + u], ri = rinv[i + u];
 #pragma unroll
       for (int c = 0; c < VW; c++) {
@@ -868,47 +734,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
       }
     }
   };
-  const int64_t ng = n / CUN;
   int64_t i = 0;
-  if constexpr (PF && S16 && VW <= 2) {
+  if constexpr (S16) {
     constexpr int NB = PFD + 1;                // as k_col_means
-    uint32_t w[NB][CUN];
+    const int64_t ng = n / CU;
+    uint32_t w[NB][CU];
 #pragma unroll
     for (int b = 0; b < PFD; b++)
-      if (b < ng) ld_raw<VW, CUN, NTL>(s16, b * CUN, ld, j0, w[b]);
+      if (b < ng) ld_raw(s16, b * CU, ld, j0, w[b]);
     for (int64_t g = 0; g < ng; g += NB) {
 #pragma unroll
       for (int b = 0; b < NB; b++) {
         const int64_t gg = g + b;
         if (gg >= ng) break;
-        if (gg + PFD < ng) ld_raw<VW, CUN, NTL>(s16, (gg + PFD) * CUN, ld, j0, w[(b + PFD) % NB]);
-        int32_t v[CUN][VW];
-        unpack_raw<VW, CUN>(w[b], v);
-        do_grp(v, gg * CUN);
+        if (gg + PFD < ng) ld_raw(s16, (gg + PFD) * CU, ld, j0, w[(b + PFD) % NB]);
+        int32_t v[CU][VW];
+        unpack_raw(w[b], v);
+        do_grp(v, gg * CU);
       }
     }
-    i = ng * CUN;
-  } else if constexpr (PF) {
-    int32_t va[CUN][VW], vb[CUN][VW];
-    if (ng > 0) ld_grp(va, 0);
-    for (int64_t g = 0; g < ng; g += 2) {
-      if (g + 1 < ng) ld_grp(vb, (g + 1) * CUN);
-      do_grp(va, g * CUN);
-      if (g + 1 >= ng) break;
-      if (g + 2 < ng) ld_grp(va, (g + 2) * CUN);
-      do_grp(vb, (g + 1) * CUN);
-    }
-    i = ng * CUN;
+    i = ng * CU;
   } else {
-    for (; i + CUN <= n; i += CUN) {
-      int32_t v[CUN][VW];
+    for (; i + CU <= n; i += CU) {
+      int32_t v[CU][VW];
       ld_grp(v, i);
       do_grp(v, i);
     }
   }
   for (; i < n; i++) {
     int32_t v[VW];
-    load_row<VW, S16, NTL>(q, s16, i, ld, j0, v);
+    load_row<S16, NTL>(q, s16, i, ld, j0, v);
 #pragma unroll
     for (int c = 0; c < VW; c++) {
       double y;
@@ -942,9 +797,6 @@ __global__ void k_zprep(const int32_t *__restrict__ sel, int64_t r, const double
 }
 
 constexpr int ZR = 8;    // rows per zquant batch
-constexpr int Z7RGS = 0, Z7CBW = 64;   // k_zquant7 grid walk (see the launch)
-constexpr bool Z7W16 = true;           // k_zquant7 16-B loads (see the launch)
-constexpr bool Z7PAIR = false;         // k_zquant7 paired 16-B stores (see the launch)
 
 // The row means / reciprocals of rows i0 .. i0+R-1 (clamped to n-1), all
 // loaded before any is used: a load inside the row loop, behind its
@@ -977,21 +829,6 @@ constexpr int ZRB = 1;   // row batches per thread (4 measured slower: 22.6 vs 2
 // farther than delta from every half-integer, rint(t') IS k, and when it is
 // also farther than delta from 0 its sign is z's sign ("-0.00").  Otherwise
 // (probability ~1e-4 per cell) the exact fp64 chain below decides.
-// Select code d (0..7) of the 8 consecutive uint16 in (a, b).
-__device__ __forceinline__ uint32_t pick8u16(const uint2 &a, const uint2 &b, int d) {
-  const uint2 h = (d & 4) ? b : a;
-  const uint32_t w = (d & 2) ? h.y : h.x;
-  return (d & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
-
-// Select element d (0..7) of the 8 consecutive ints (a, b).
-__device__ __forceinline__ int32_t pick8(const int4 &a, const int4 &b, int d) {
-  const int4 h = (d & 4) ? b : a;
-  return (d & 2) ? ((d & 1) ? h.w : h.z) : ((d & 1) ? h.y : h.x);
-}
-
-// zquant_rows: below the kernel body helpers (defined before use).
-
 
 // Pick element c (0..3) of a 4-vector held in registers (selects, no scratch).
 // (Masks, not a ternary chain: the compiler turns the chain back into an
@@ -1114,12 +951,9 @@ __device__ __forceinline__ void zquant_rows(const int32_t (&qv)[ZR][4], GETQ get
   }
 }
 
-// q reads: a thread's 4 selected columns usually lie within 8 consecutive
-// source columns (the selection keeps ~90 % of them), so each row is read
-// as two aligned int4 loads and the 4 values picked in registers; 4 dword
-// gathers per row (16 B used per 64-B line each) took 2x the HBM time.
-// Threads whose columns spread wider gather them one by one.
-template <bool VEC, bool S16>
+// The fallback for an int32 matrix whose rows are not 16-byte aligned (every
+// other layout goes through k_zquant6 / k_zquant7): 4 dword gathers per row.
+// (s16 is unused; it keeps the argument layout of the other zquant kernels.)
 __global__ __launch_bounds__(256) void k_zquant4(const int32_t *__restrict__ q, Q16 s16, int64_t n, int64_t ld,
                                                  const int32_t *__restrict__ sel, int64_t r,
                                                  const double *__restrict__ rm, const double *__restrict__ rinv,
@@ -1144,80 +978,19 @@ __global__ __launch_bounds__(256) void k_zquant4(const int32_t *__restrict__ q, 
     m32[c] = mc.x;
     c32[c] = mc.y;
   }
-  // two aligned loads cover 8 columns: int4 pairs (int32) or uint2 pairs (compact)
-  const int64_t base = js[0] & ~3ll;
-  const bool fast = (S16 || VEC) && js[w - 1] - base < 8 && base + 8 <= ld;
-  int d[4];
-#pragma unroll
-  for (int c = 0; c < 4; c++) d[c] = (int)(js[c] - base);
   for (int b = 0; b < ZRB; b++) {
     const int64_t i0 = ((int64_t)blockIdx.y * ZRB + b) * ZR;
     if (i0 >= n) break;
     const int64_t i1 = (i0 + ZR < n) ? i0 + ZR : n;
     int32_t qv[ZR][4];
-    if (S16 && fast) {
-      uint2 va[ZR], vb[ZR];
 #pragma unroll
-      for (int u = 0; u < ZR; u++) {
-        const int64_t i = (i0 + u < i1) ? i0 + u : i0;
-        const uint2 *p = reinterpret_cast<const uint2 *>(s16.q + i * ld + base);
-        va[u] = p[0];
-        vb[u] = p[1];
-      }
-      uint32_t mx = 0;
+    for (int u = 0; u < ZR; u++)
 #pragma unroll
-      for (int u = 0; u < ZR; u++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-          const uint32_t code = pick8u16(va[u], vb[u], d[c]);
-          qv[u][c] = (int32_t)code;
-          mx = max(mx, (i0 + u < i1 && c < w) ? code : 0u);
-        }
-      if (__builtin_expect(mx > GRID_Q16_MAXV, 0)) {       // rare: missing / escapes
-#pragma unroll
-        for (int u = 0; u < ZR; u++)
-#pragma unroll
-          for (int c = 0; c < 4; c++)
-            if (i0 + u < i1 && c < w && (uint32_t)qv[u][c] > GRID_Q16_MAXV)
-              qv[u][c] = q16_slow((uint32_t)qv[u][c], i0 + u, js[c], s16);
-      }
-#pragma unroll
-      for (int u = 0; u < ZR; u++)
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-          if (!(i0 + u < i1 && c < w)) qv[u][c] = GRID_MISSING;
-    } else if (S16) {
-#pragma unroll
-      for (int u = 0; u < ZR; u++)
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-          qv[u][c] = (i0 + u < i1 && c < w) ? q16_val(s16.q[(i0 + u) * ld + js[c]], i0 + u, js[c], s16)
-                                             : GRID_MISSING;
-    } else if (fast) {
-      int4 va[ZR], vb[ZR];
-#pragma unroll
-      for (int u = 0; u < ZR; u++) {
-        const int64_t i = (i0 + u < i1) ? i0 + u : i0;
-        const int4 *p = reinterpret_cast<const int4 *>(q + i * ld + base);
-        va[u] = p[0];
-        vb[u] = p[1];
-      }
-#pragma unroll
-      for (int u = 0; u < ZR; u++)
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-          qv[u][c] = (i0 + u < i1 && c < w) ? pick8(va[u], vb[u], d[c]) : GRID_MISSING;
-    } else {
-#pragma unroll
-      for (int u = 0; u < ZR; u++)
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-          qv[u][c] = (i0 + u < i1 && c < w) ? q[(i0 + u) * ld + js[c]] : GRID_MISSING;
-    }
+      for (int c = 0; c < 4; c++)
+        qv[u][c] = (i0 + u < i1 && c < w) ? q[(i0 + u) * ld + js[c]] : GRID_MISSING;
     auto getq = [&](int u, int c) -> int32_t {
       const int64_t j = sel4(js, c);
-      if constexpr (S16) return q16_val(s16.q[(i0 + u) * ld + j], i0 + u, j, s16);
-      else return q[(i0 + u) * ld + j];
+      return q[(i0 + u) * ld + j];
     };
     zquant_rows(qv, getq, s0, i0, i1, w, cm, m32, c32, rm, rinv, mus, sq, rsq, scale, zq, ld_zq, qmax, zb, ld_zb,
                 kbs, overflow);
@@ -1514,14 +1287,12 @@ __global__ __launch_bounds__(256) void k_zquant6(const int32_t *__restrict__ q, 
 // sel[s] usually lie in the 8 codes at base = sel[s0] & ~3: two aligned 8-B
 // loads per row and a register pick (bfe); other lanes gather per cell.
 // Fast path, acceptance test and deferred exact chain: as zquant_rows.
-// PROBE (tools build only, wrong results): bit 0 no z stores, bit 1 no panel
-// stores, bit 2 no loads (codes from a constant).
 // 106 VGPRs, 4 workgroups per CU (forcing 5 spilled 12 VGPRs: 19.0 vs 15.5 ms).
 // W16: 16-B loads (the metadata of a lane's 4 columns as int4 / float4, and a
 // 16-code window at sel[s0] & ~7 as two 16-B loads per row instead of three
 // 8-B loads): the texture data path, not HBM, bounds this kernel (PMC: TD busy
 // 99 %, TA 82 %), and it costs per wave-instruction, not per byte.
-template <int NT, int PROBE, bool W16, bool PAIR>
+template <int NT, bool W16>
 __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const int32_t *__restrict__ sel,
                                                  int64_t r, const double *__restrict__ rm,
                                                  const double *__restrict__ rinv, const double *__restrict__ mus,
@@ -1530,34 +1301,11 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
                                                  int16_t *__restrict__ zq, int64_t ld_zq,
                                                  const int32_t *__restrict__ colmap, int32_t qmax,
                                                  uint16_t *__restrict__ zb, int64_t ld_zb, int64_t kbs,
-                                                 int32_t *__restrict__ overflow, int rpw, ZEsc esc,
-                                                 int rgs, int cbw, int zblk) {
-  // (row group, column block) of this workgroup: the 2-D grid (x = row group) when
-  // rgs == 0, else a 1-D grid walked in super-tiles of rgs row groups x cbw column
-  // blocks (placement only; every (row group, column block) is visited once)
-  int64_t bx = blockIdx.x, by = blockIdx.y;
-  if (rgs > 0) {
-    const int64_t nrg = (n + rpw - 1) / rpw, ncb = ((r + 3) / 4 + 255) / 256;
-    const int64_t L = blockIdx.x, sr = L / (rgs * ncb), brg = sr * rgs;
-    const int64_t h = nrg - brg < rgs ? nrg - brg : rgs;
-    const int64_t rem = L - sr * rgs * ncb, st = rem / (h * cbw), bcb = st * cbw;
-    const int64_t wd = ncb - bcb < cbw ? ncb - bcb : cbw;
-    const int64_t t = rem - st * h * cbw;
-    if (wd == cbw && (cbw & 7) == 0) {   // XCD L % 8 keeps the column blocks bcb + 8 g + (t % 8)
-      const int64_t k = t >> 3;
-      bx = brg + k % h;
-      by = bcb + (k / h) * 8 + (t & 7);
-    } else {
-      bx = brg + t % h;
-      by = bcb + t / h;
-    }
-  }
+                                                 int32_t *__restrict__ overflow, int rpw, ZEsc esc) {
+  // workgroup = (row group, column block) of a 2-D grid, row groups fastest
+  const int64_t bx = blockIdx.x, by = blockIdx.y;
   const int64_t s0 = (by * 256 + threadIdx.x) * 4;
   if (s0 >= r) return;
-  if (zblk & 1) {   // timing probe (tools build): step-4 output blocked [col block][row][1024]
-    zq += by * (n - 1) * 1024;
-    ld_zq = 1024;
-  }
   const int w = (int)((r - s0) < 4 ? (r - s0) : 4);
   const int64_t r0 = bx * rpw;
   const int64_t r1 = (r0 + rpw < n) ? r0 + rpw : n;
@@ -1607,8 +1355,8 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
   }
   // W16: the upper 16 B of the window only for a lane whose columns reach past
   // its first 8 codes (about half of them at 90 % selected); the others would
-  // select nothing from it.  zblk bit 1 (tools build): always load it (A/B)
-  const bool ld_hi = nwin >= 16 && (need_hi || (zblk & 2));
+  // select nothing from it
+  const bool ld_hi = nwin >= 16 && need_hi;
   // byte-permute selectors of code c: the 8-B piece it is not in selects zero
   // bytes (0x0c), so code = perm(va) | perm(vb) | perm(vc), branch-free
   uint32_t pa[4], pb[4], pc[4], pd[4];
@@ -1632,12 +1380,7 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
   for (int u = 0; u < ZR; u++) {
     const int64_t i = (r0 + u < r1) ? r0 + u : r0;
     const uint16_t *p = s16.q + i * ld + base;
-    if constexpr (PROBE & 4) {
-      va[u] = v2u{0x0FA00FA0u + (uint32_t)u, 0x0FA00FA0u};
-      vb[u] = va[u];
-      vc[u] = va[u];
-      vd[u] = va[u];
-    } else if constexpr (W16) {
+    if constexpr (W16) {
       typedef unsigned v4u __attribute__((ext_vector_type(4)));
       const v4u lo = NT & 1 ? __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p))
                             : *reinterpret_cast<const v4u *>(p);
@@ -1665,11 +1408,9 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
   const float qf = (float)qmax;
   uint32_t slowm = 0;
   int of = 0;
-  // HOT (wave-uniform): every lane has 4 columns, all in its 8-code window,
-  // 8-B stores for both outputs -- no per-cell branches; otherwise the
-  // general body (tail lanes, gathers, element stores)
-  auto rows = [&](auto hot_c) {
-    constexpr bool HOT = decltype(hot_c)::value;
+  // The general body (tail lanes, gathers, element stores), for a wave that
+  // cannot take the hot one below
+  auto general_rows = [&]() {
 #pragma unroll
     for (int u = 0; u < ZR; u++) {
       const int64_t i = r0 + u;
@@ -1683,8 +1424,8 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
         uint32_t code = __builtin_amdgcn_perm(va[u].y, va[u].x, pa[c]) | __builtin_amdgcn_perm(vb[u].y, vb[u].x, pb[c]) |
                         __builtin_amdgcn_perm(vc[u].y, vc[u].x, pc[c]) |
                         (W16 ? __builtin_amdgcn_perm(vd[u].y, vd[u].x, pd[c]) : 0u);
-        if (!HOT && !inwin && c < w && !(d[c] < nwin)) code = s16.q[i * ld + js[c]];   // gather
-        const bool valid = (HOT || c < w) && rowok && code != GRID_Q16_MISS;
+        if (!inwin && c < w && !(d[c] < nwin)) code = s16.q[i * ld + js[c]];   // gather
+        const bool valid = c < w && rowok && code != GRID_Q16_MISS;
         const float y = (float)(int32_t)code * a32;
         const float t = (y - m32[c]) * c32[c];
         const float kk = rintf(t);
@@ -1701,16 +1442,14 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
         zc[c] = (uint32_t)cd & 0xFFFFu;
         slowm |= defer ? (1u << (u * 4 + c)) : 0u;
       }
-      if (HOT || vec_zq) {
+      if (vec_zq) {
         *reinterpret_cast<uint2 *>(zq + i * ld_zq + s0) = make_uint2(zc[0] | (zc[1] << 16), zc[2] | (zc[3] << 16));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; c++)
           if (c < w) zq[i * ld_zq + s0 + c] = (int16_t)zc[c];
       }
-      if (HOT) {
-        *reinterpret_cast<uint2 *>(zb + zb0 + i * zbs) = make_uint2(bv[0] | (bv[1] << 16), bv[2] | (bv[3] << 16));
-      } else if (zb) {
+      if (zb) {
         if (vec_zb) {
           *reinterpret_cast<uint2 *>(zb + zbi(i, cm[0])) = make_uint2(bv[0] | (bv[1] << 16), bv[2] | (bv[3] << 16));
         } else {
@@ -1721,7 +1460,8 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
       }
     }
   };
-  // HOT body: no per-cell branch or mask.  A code outside the lane's window,
+  // HOT body (wave-uniform: every lane has 4 columns and 8-B stores for both
+  // outputs): no per-cell branch or mask.  A code outside the lane's window,
   // a missing cell or an escape is computed from garbage and DEFERRED (the
   // exact loop below gathers it); a row with a zero / NaN mean (uniform) is
   // written as NaN codes directly.
@@ -1787,51 +1527,14 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
       if (i >= r1) break;
       uint32_t z0, z1, b0, b1;
       hot_row(u, outm, cy, cm2, z0, z1, b0, b1);
-      if (!(PROBE & 1)) *reinterpret_cast<uint2 *>(zq + i * ld_zq + s0) = make_uint2(z0, z1);
-      if (!(PROBE & 2)) *reinterpret_cast<uint2 *>(zb + zb0 + i * zbs) = make_uint2(b0, b1);
-      if (PROBE) slowm = 0;
-    }
-  };
-  // PAIRED stores (a full row group): lanes 2k and 2k+1 swap halves with one
-  // DPP move per dword, so the even lane stores 16 B of row u (its 4 cells and
-  // its partner's) and the odd lane 16 B of row u+1: half the store
-  // instructions (the texture path costs per wave-instruction)
-  auto hot_pairs = [&]() {
-    uint32_t outm;
-    float cy[4], cm2[4];
-    hot_prep(outm, cy, cm2);
-    const bool odd = threadIdx.x & 1;
-    auto swp = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false); };
-#pragma unroll
-    for (int u = 0; u < ZR; u += 2) {
-      uint32_t za0, za1, ba0, ba1, zb0_, zb1_, bb0, bb1;
-      hot_row(u, outm, cy, cm2, za0, za1, ba0, ba1);
-      hot_row(u + 1, outm, cy, cm2, zb0_, zb1_, bb0, bb1);
-      const uint32_t rz0 = swp(odd ? za0 : zb0_), rz1 = swp(odd ? za1 : zb1_);
-      const uint32_t rb0 = swp(odd ? ba0 : bb0), rb1 = swp(odd ? ba1 : bb1);
-      const int64_t i = r0 + u + (odd ? 1 : 0);
-      const int64_t sh = odd ? 4 : 0;
-      if (!(PROBE & 1))
-        *reinterpret_cast<uint4 *>(zq + i * ld_zq + s0 - sh) =
-            odd ? make_uint4(rz0, rz1, zb0_, zb1_) : make_uint4(za0, za1, rz0, rz1);
-      if (!(PROBE & 2))
-        *reinterpret_cast<uint4 *>(zb + zb0 - sh + i * zbs) =
-            odd ? make_uint4(rb0, rb1, bb0, bb1) : make_uint4(ba0, ba1, rb0, rb1);
-      if (PROBE) slowm = 0;
+      *reinterpret_cast<uint2 *>(zq + i * ld_zq + s0) = make_uint2(z0, z1);
+      *reinterpret_cast<uint2 *>(zb + zb0 + i * zbs) = make_uint2(b0, b1);
     }
   };
   // wave-uniform test (lanes past r have returned)
   const bool hot = __all(w == 4 && vec_zq && vec_zb && zb != nullptr);
-  // pairing: the partner lane holds the next 4 columns of both outputs and the
-  // pair's 8 panel columns are 16-B aligned (a disabled partner reads INT_MIN)
-  const int cmp = __builtin_amdgcn_update_dpp((int)0x80000000, cm[0], 0xB1, 0xF, 0xF, false);
-  const bool podd = threadIdx.x & 1;
-  const bool pair = PAIR && hot && r1 - r0 == ZR && (ld_zq & 7) == 0 && ((uintptr_t)zq & 15) == 0 &&
-                    ((kbs > 0 ? kbs : ld_zb) & 7) == 0 && ((uintptr_t)zb & 15) == 0 &&
-                    __all(podd ? cmp == cm[0] - 4 : (cmp == cm[0] + 4 && (cm[0] & 7) == 0));
-  if (pair) hot_pairs();
-  else if (hot) hot_rows();
-  else rows(std::integral_constant<bool, false>());
+  if (hot) hot_rows();
+  else general_rows();
   if (__builtin_expect(slowm != 0, 0)) {          // exact fp64 chain (rare), after the fast stores
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll 1
@@ -1864,9 +1567,8 @@ __device__ __forceinline__ void z7_body(Q16 s16, int64_t n, int64_t ld, const in
   if (of) atomicOr(overflow, of);
 }
 
-// k_zquant7 at 4 waves per SIMD (<= 128 VGPRs); the paired-store variant
-// also at 3 (its 130 VGPRs spill 9 at 4).
-template <int NT, int PROBE = 0, bool W16 = false, bool PAIR = false>
+// k_zquant7 at 4 waves per SIMD (<= 128 VGPRs).
+template <int NT, bool W16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_zquant7(Q16 s16, int64_t n, int64_t ld, const int32_t *__restrict__ sel,
                                                  int64_t r, const double *__restrict__ rm,
                                                  const double *__restrict__ rinv, const double *__restrict__ mus,
@@ -1875,22 +1577,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                                                  int16_t *__restrict__ zq, int64_t ld_zq,
                                                  const int32_t *__restrict__ colmap, int32_t qmax,
                                                  uint16_t *__restrict__ zb, int64_t ld_zb, int64_t kbs,
-                                                 int32_t *__restrict__ overflow, int rpw, ZEsc esc,
-                                                 int rgs, int cbw, int zblk) {
-  z7_body<NT, PROBE, W16, PAIR>(s16, n, ld, sel, r, rm, rinv, mus, sq, rsq, mc32, scale, zq, ld_zq, colmap, qmax, zb, ld_zb, kbs, overflow, rpw, esc, rgs, cbw, zblk);
-}
-template <int NT, int PROBE = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_zquant7p3(Q16 s16, int64_t n, int64_t ld, const int32_t *__restrict__ sel,
-                                                 int64_t r, const double *__restrict__ rm,
-                                                 const double *__restrict__ rinv, const double *__restrict__ mus,
-                                                 const double *__restrict__ sq, const double *__restrict__ rsq,
-                                                 const float2 *__restrict__ mc32, double scale,
-                                                 int16_t *__restrict__ zq, int64_t ld_zq,
-                                                 const int32_t *__restrict__ colmap, int32_t qmax,
-                                                 uint16_t *__restrict__ zb, int64_t ld_zb, int64_t kbs,
-                                                 int32_t *__restrict__ overflow, int rpw, ZEsc esc,
-                                                 int rgs, int cbw, int zblk) {
-  z7_body<NT, PROBE, true, true>(s16, n, ld, sel, r, rm, rinv, mus, sq, rsq, mc32, scale, zq, ld_zq, colmap, qmax, zb, ld_zb, kbs, overflow, rpw, esc, rgs, cbw, zblk);
+                                                 int32_t *__restrict__ overflow, int rpw, ZEsc esc) {
+  z7_body<NT, W16>(s16, n, ld, sel, r, rm, rinv, mus, sq, rsq, mc32, scale, zq, ld_zq, colmap, qmax, zb, ld_zb, kbs, overflow, rpw, esc);
 }
 
 // Independent check of the step-4 output and the step-5 panel (tests): every
@@ -2076,33 +1764,10 @@ static int row_blocks_impl(grid_ctx *ctx, const int32_t *d_q, const Q16 &s16, in
     const char *rn = getenv("GRID_ROWBLK_NT");
     const bool nt = rn ? atoi(rn) != 0 : ROWBLK_NT;
     if (c16) {
-      const char *pe = GRID_AB_KNOB("GRID_ROWBLK16_PB");
-      const int pb = pe ? atoi(pe) : RB16_PB;
-      REQUIRE(pb == 0 || pb == 1 || pb == 2 || pb == 4, "GRID_ROWBLK16_PB must be 0, 1, 2 or 4 (got %d)", pb);
-      if (pb == 0) {
-        // streamed: 8 resident workgroups per CU (17.9 KiB of LDS each), at most one per unit
-        const char *we = GRID_AB_KNOB("GRID_ROWBLK16_WPC");
-        const int64_t wpc = we && atoi(we) > 0 ? atoi(we) : 8;
-        const int64_t g = std::min<int64_t>(n * nfull, (int64_t)ctx->ncu * wpc);
-        hipLaunchKernelGGL(nt ? k_row_blocks16s<true> : k_row_blocks16s<false>, dim3((unsigned)g), dim3(256), 0,
-                           ctx->stream, s16, ld, n, nfull, nblk, d_bsum, d_bcnt);
-      } else {
-        // the plain blocks' sums by lane exchanges (default) or by rb_finish's broadcasts (A/B)
-        const char *xe = GRID_AB_KNOB("GRID_ROWBLK16_XOR");
-        const bool xr = xe ? atoi(xe) != 0 : true;
-        auto kern = pb == 1 ? (nt ? (xr ? k_row_blocks16<1, true> : k_row_blocks16<1, true, false>)
-                                  : k_row_blocks16<1, false>)
-                  : pb == 2 ? (nt ? k_row_blocks16<2, true> : k_row_blocks16<2, false>)
-                            : (nt ? k_row_blocks16<4, true> : k_row_blocks16<4, false>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(nfull, pb), (unsigned)n), dim3(256), 0, ctx->stream, s16,
-                           ld, nfull, nblk, d_bsum, d_bcnt);
-      }
+      hipLaunchKernelGGL(nt ? k_row_blocks16<true> : k_row_blocks16<false>, dim3((unsigned)nfull, (unsigned)n),
+                         dim3(256), 0, ctx->stream, s16, ld, nfull, nblk, d_bsum, d_bcnt);
     } else {
-      const char *xe = GRID_AB_KNOB("GRID_ROWBLK16_XOR");   // the same A/B for the int32 kernel
-      const bool xr = xe ? atoi(xe) != 0 : true;
-      auto kern = vec4_ok(d_q, ld) ? (nt ? (xr ? k_row_blocks_full<3> : k_row_blocks_full<3, false>)
-                                         : k_row_blocks_full<0>)
-                                   : k_row_blocks_full<1>;
+      auto kern = vec4_ok(d_q, ld) ? (nt ? k_row_blocks_full<3> : k_row_blocks_full<0>) : k_row_blocks_full<1>;
       hipLaunchKernelGGL(kern, dim3((unsigned)nfull, (unsigned)n), dim3(256), 0, ctx->stream, d_q, s16, ld, nfull,
                          nblk, d_bsum, d_bcnt);
     }
@@ -2272,56 +1937,22 @@ static int col_stats_impl(grid_ctx *ctx, bool vars, const int32_t *d_q, const Q1
   uint8_t *rbad;
   int rc = recip_rows(ctx, d_rm, n, 0, &rinv, &rest, &rbad);
   if (rc) return rc;
-  // int32: 1 column per thread (47 k waves at the bench shape, ~6 rounds of
-  // resident waves; 4 per thread left a 2.3-round tail: 14.5 vs 13.7 ms)
-#ifdef GRID_PROBES
-  // tools build only: column-width / workgroup-shape alternatives (A/B)
-  const char *cv = GRID_AB_KNOB("GRID_COL_VW"), *cu = GRID_AB_KNOB("GRID_COL_CU");
-  const int want = cv ? atoi(cv) : 1;
-  const bool cu16 = cu && atoi(cu) == 16;
-#else
-  const int want = 1;
-  const char *cu = GRID_AB_KNOB("GRID_COL16_CU");   // compact codes: 16 rows in flight (timing only)
-  const bool cu16 = s16.q && cu && atoi(cu) == 16;
-#endif
-  const char *cpf = GRID_AB_KNOB("GRID_COL_PF");  // software-pipelined row groups, compact 1- and 2-column paths (A/B)
-  const bool pf = cpf ? atoi(cpf) != 0 : COL_PF;
-  const char *cn = getenv("GRID_COL_NT");   // streaming (nontemporal) loads, 1-column path (A/B)
+  // GRID_COL_NT: streaming (nontemporal) loads of the int32 matrix (A/B).  It
+  // has no effect on the compact path, whose loads are always streaming.
+  const char *cn = getenv("GRID_COL_NT");
   const bool nt = cn ? atoi(cn) != 0 : COL_NT;
-  // compact codes: GRID_COL16_VW columns per thread (1: 2-B loads, 2: 4-B loads, the default; timing only)
-  const char *c16v = GRID_AB_KNOB("GRID_COL16_VW");
-  const int vw16 = c16v ? atoi(c16v) : COL16_VW;
-  REQUIRE(vw16 == 1 || vw16 == 2 || vw16 == 4 || vw16 == 8, "GRID_COL16_VW must be 1, 2, 4 or 8 (got %d)", vw16);
-  // 16-B rows (VW 8) need 16-B aligned rows of the compact matrix
-  const int vw = s16.q ? (vw16 == 8 && (ld % 8 != 0 || (uintptr_t)s16.q % 16 != 0) ? 4 : vw16)
-                       : vec4_ok(d_q, ld) ? (want == 4 ? 4 : want == 1 ? 1 : 2) : 1;
+  const bool c16 = s16.q != nullptr;
+  const int vw = c16 ? COL_VW<true> : COL_VW<false>;
   const dim3 grid((unsigned)ceil_div(ceil_div(m, vw), 256));
-  // less than one round of resident waves (8 per SIMD): the deep-prefetch form
-  const bool deep = s16.q && vw == 2 && pf && !cu16 &&
-                    ceil_div(ceil_div(m, vw), 64) < (int64_t)(ctx->ncu > 0 ? ctx->ncu : 256) * 4 * 8;
+  // compact codes, less than one round of resident waves (8 per SIMD): the deep-prefetch form
+  const bool deep = c16 && ceil_div(ceil_div(m, vw), 64) < (int64_t)(ctx->ncu > 0 ? ctx->ncu : 256) * 4 * 8;
   if (!vars) {
-    auto kern = s16.q ? (vw == 8 ? (nt ? k_col_means<8, true, CU, true> : k_col_means<8, true>) : vw == 4 ? k_col_means<4, true>
-                         : vw == 2 ? (pf ? (cu16 ? k_col_means<2, true, 16, true, true>
-                                           : deep ? k_col_means<2, true, CU, true, true, 4, 3>
-                                                  : k_col_means<2, true, CU, true, true, 8>)
-                                      : cu16 ? k_col_means<2, true, 16, true>
-                                      : nt ? k_col_means<2, true, CU, true> : k_col_means<2, true>)
-                                   : pf ? (cu16 ? k_col_means<1, true, 16, true, true> : k_col_means<1, true, CU, true, true>)
-                                        : (nt ? k_col_means<1, true, CU, true> : k_col_means<1, true>))
-                : vw == 4 ? k_col_means<4, false> : vw == 2 ? k_col_means<2, false>
-                : cu16 ? k_col_means<1, false, 16> : nt ? k_col_means<1, false, CU, true> : k_col_means<1, false>;
+    auto kern = c16 ? (deep ? k_col_means<true, true, 4, 3> : k_col_means<true, true, 8, 1>)
+                    : (nt ? k_col_means<false, true> : k_col_means<false, false>);
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, d_q, s16, n, m, ld, d_rm, rinv, rbad, d_out);
   } else {
-    auto kern = s16.q ? (vw == 8 ? (nt ? k_col_vars<8, true, CU, true> : k_col_vars<8, true>) : vw == 4 ? k_col_vars<4, true>
-                         : vw == 2 ? (pf ? (cu16 ? k_col_vars<2, true, 16, true, true>
-                                           : deep ? k_col_vars<2, true, CU, true, true, 4, 3>
-                                                  : k_col_vars<2, true, CU, true, true, 8>)
-                                      : cu16 ? k_col_vars<2, true, 16, true>
-                                      : nt ? k_col_vars<2, true, CU, true> : k_col_vars<2, true>)
-                                   : pf ? (cu16 ? k_col_vars<1, true, 16, true, true> : k_col_vars<1, true, CU, true, true>)
-                                        : (nt ? k_col_vars<1, true, CU, true> : k_col_vars<1, true>))
-                : vw == 4 ? k_col_vars<4, false> : vw == 2 ? k_col_vars<2, false>
-                : cu16 ? k_col_vars<1, false, 16> : nt ? k_col_vars<1, false, CU, true> : k_col_vars<1, false>;
+    auto kern = c16 ? (deep ? k_col_vars<true, true, 4, 3> : k_col_vars<true, true, 8, 1>)
+                    : (nt ? k_col_vars<false, true> : k_col_vars<false, false>);
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, d_q, s16, n, m, ld, d_rm, rinv, rbad, d_mu, d_out,
                        d_ratio);
   }
@@ -2388,14 +2019,9 @@ static int zquant_impl(grid_ctx *ctx, const int32_t *d_q, const Q16 &s16, int64_
   hipLaunchKernelGGL(k_zprep, dim3((unsigned)ceil_div(r, 256)), dim3(256), 0, ctx->stream, d_sel, r, d_mu, scale, mus,
                      sq, rsq, mc32);
   LAUNCHCHK();
-#ifdef GRID_PROBES
-  const char *zv = getenv("GRID_ZQUANT_VARIANT");   // tools build: 4 = the selected-column kernel (A/B)
-#else
-  const char *zv = nullptr;
-#endif
   const bool c16 = s16.q != nullptr;
   REQUIRE(!d_zq16 || c16 || vec4_ok(d_q, ld), "int16 z output needs the int32 depth layout (ld % 4 == 0)");
-  if (d_zq16 || c16 || (vec4_ok(d_q, ld) && !(zv && atoi(zv) == 4))) {
+  if (d_zq16 || c16 || vec4_ok(d_q, ld)) {
     int32_t *sidx = (int32_t *)(rest + 4 * rb);
     HIPCHK(hipMemsetAsync(sidx, 0xFF, (size_t)ld * 4, ctx->stream));
     hipLaunchKernelGGL(k_sidx, dim3((unsigned)ceil_div(r, 256)), dim3(256), 0, ctx->stream, d_sel, r, sidx);
@@ -2409,58 +2035,25 @@ static int zquant_impl(grid_ctx *ctx, const int32_t *d_q, const Q16 &s16, int64_
     const dim3 g6((unsigned)ceil_div(n, rpw), (unsigned)ceil_div(ceil_div(ld, 4), 256));
 #define Z6_PICK(ZT, CS) (nt ? (rpw > ZR ? k_zquant6<true, ZT, 1, CS> : k_zquant6<false, ZT, 1, CS>)                    \
                             : (rpw > ZR ? k_zquant6<true, ZT, 0, CS> : k_zquant6<false, ZT, 0, CS>))
-    const char *z7e = GRID_AB_KNOB("GRID_ZQUANT7");        // compact source, int16 output: 1 (default) = k_zquant7
-    const bool z7 = c16 && d_zq16 && (!z7e || atoi(z7e) != 0);
-    if (z7) {
-      // k_zquant7 reads overlapping 24-B windows: plain loads (the rows' lines
-      // serve neighbouring lanes from L2) unless GRID_ZQUANT_NT=1 (15.7 vs 17.8 ms)
+    if (c16 && d_zq16) {
+      // compact source, int16 output: k_zquant7, one row group per workgroup
+      // (GRID_ZQUANT_GROUPS does not apply).  It reads overlapping 24-B
+      // windows: plain loads (the rows' lines serve neighbouring lanes from
+      // L2) unless GRID_ZQUANT_NT=1 (15.7 vs 17.8 ms)
       const bool nt7 = ntv && atoi(ntv) == 1;
-      // 16-B loads (GRID_Z7_W16, timing A/B; results identical); needs 16-B aligned operands
-      const char *w16e = GRID_AB_KNOB("GRID_Z7_W16");
-      const bool w16 = (w16e ? atoi(w16e) != 0 : Z7W16) && (ld % 8) == 0 && ((uintptr_t)s16.q % 16) == 0 &&
-                       ((uintptr_t)d_sel % 16) == 0 && (!d_colmap || ((uintptr_t)d_colmap % 16) == 0) &&
-                       ((uintptr_t)mc32 % 16) == 0;
-      // paired 16-B stores (GRID_Z7_PAIR, timing A/B; results identical; with the 16-B loads)
-      const char *pre = GRID_AB_KNOB("GRID_Z7_PAIR");
-      const int pr7v = pre ? atoi(pre) : (Z7PAIR ? 1 : 0);   // 2: the pair variant at 3 waves/SIMD
-      const bool pr7 = pr7v != 0 && w16;
+      // 16-B loads need 16-B aligned operands; otherwise the 8-B form (results identical)
+      const bool w16 = (ld % 8) == 0 && ((uintptr_t)s16.q % 16) == 0 && ((uintptr_t)d_sel % 16) == 0 &&
+                       (!d_colmap || ((uintptr_t)d_colmap % 16) == 0) && ((uintptr_t)mc32 % 16) == 0;
       REQUIRE(ceil_div(ceil_div(r, 4), 256) <= 65535, "r too large for one launch");
-      // super-tiles of rgs row groups x cbw column blocks (GRID_Z7_RGS / GRID_Z7_CBW; RGS=0: the 2-D grid,
-      // row groups fastest)
-      const char *rge = GRID_AB_KNOB("GRID_Z7_RGS"), *cbe = GRID_AB_KNOB("GRID_Z7_CBW");
-      const int rgs = rge ? atoi(rge) : Z7RGS, cbw = cbe ? atoi(cbe) : Z7CBW;
-      REQUIRE(rgs >= 0 && cbw > 0, "GRID_Z7_RGS must be >= 0 and GRID_Z7_CBW > 0");
-      const int64_t nrg7 = ceil_div(n, ZR), ncb7 = ceil_div(ceil_div(r, 4), 256);
-#ifdef GRID_PROBES
-      const char *zbe = getenv("GRID_Z7_ZBLK");     // wrong escape positions: timing only
-      const char *hae = getenv("GRID_Z7_HIALL");    // 1: every lane loads its window's upper 16 B (A/B)
-      const int zblk = (zbe && atoi(zbe) ? 1 : 0) | (hae && atoi(hae) ? 2 : 0);
-      REQUIRE(!(zblk & 1) || ld_zq >= ncb7 * 1024, "GRID_Z7_ZBLK needs ld_zq >= %lld", (long long)(ncb7 * 1024));
-#else
-      const int zblk = 0;
-#endif
-      REQUIRE(rgs == 0 || nrg7 * ncb7 < (1ll << 31), "zquant grid too large");
-      const dim3 g7 = rgs > 0 ? dim3((unsigned)(nrg7 * ncb7)) : dim3((unsigned)nrg7, (unsigned)ncb7);
-#ifdef GRID_PROBES
-      const char *pe = getenv("GRID_Z7_PROBE");
-      const int pr = pe ? atoi(pe) : 0;
-#define Z7P(P) (w16 ? (pr7 ? (pr7v == 2 ? k_zquant7p3<0, P> : k_zquant7<0, P, true, true>) : k_zquant7<0, P, true>) \
-                     : k_zquant7<0, P>)
-      auto k7 = pr == 1 ? Z7P(1) : pr == 2 ? Z7P(2) : pr == 3 ? Z7P(3) : pr == 4 ? Z7P(4) : pr == 7 ? Z7P(7) : Z7P(0);
-#undef Z7P
-      if (nt7) k7 = w16 ? k_zquant7<1, 0, true> : k_zquant7<1>;
-#else
-      auto k7 = w16 ? (pr7 ? (pr7v == 2 ? k_zquant7p3<0, 0> : k_zquant7<0, 0, true, true>)
-                           : nt7 ? k_zquant7<1, 0, true> : k_zquant7<0, 0, true>)
-                    : (nt7 ? k_zquant7<1> : k_zquant7<0>);
-#endif
+      // 2-D grid, row groups fastest
+      const dim3 g7((unsigned)ceil_div(n, ZR), (unsigned)ceil_div(ceil_div(r, 4), 256));
+      auto k7 = w16 ? (nt7 ? k_zquant7<1, true> : k_zquant7<0, true>) : (nt7 ? k_zquant7<1, false> : k_zquant7<0, false>);
       hipLaunchKernelGGL(k7, g7, dim3(256), 0, ctx->stream, s16, n, ld, d_sel, r, d_rm,
                          rinv, mus, sq, rsq, mc32, scale, d_zq16, ld_zq, d_colmap, qmax, d_zb, ld_zb, kbs, d_of,
-                         ZR, esc, rgs, cbw, zblk);
+                         ZR, esc);
     } else if (d_zq16) {
-      auto k16 = c16 ? Z6_PICK(int16_t, true) : Z6_PICK(int16_t, false);
-      hipLaunchKernelGGL(k16, g6, dim3(256), 0, ctx->stream, d_q, s16, n, ld, sidx, d_rm, rinv, mus, sq, rsq, mc32,
-                         scale, d_zq16, ld_zq, d_colmap, qmax, d_zb, ld_zb, kbs, d_of, rpw, esc);
+      hipLaunchKernelGGL(Z6_PICK(int16_t, false), g6, dim3(256), 0, ctx->stream, d_q, s16, n, ld, sidx, d_rm, rinv, mus,
+                         sq, rsq, mc32, scale, d_zq16, ld_zq, d_colmap, qmax, d_zb, ld_zb, kbs, d_of, rpw, esc);
     } else {
       auto k32 = c16 ? Z6_PICK(int32_t, true) : Z6_PICK(int32_t, false);
       hipLaunchKernelGGL(k32, g6, dim3(256), 0, ctx->stream, d_q, s16, n, ld, sidx, d_rm, rinv, mus, sq, rsq, mc32,
@@ -2469,11 +2062,11 @@ static int zquant_impl(grid_ctx *ctx, const int32_t *d_q, const Q16 &s16, int64_
 #undef Z6_PICK
     LAUNCHCHK();
   } else {
-  auto kz = s16.q ? k_zquant4<false, true> : vec4_ok(d_q, ld) ? k_zquant4<true, false> : k_zquant4<false, false>;
-  hipLaunchKernelGGL(kz, dim3((unsigned)ceil_div(ceil_div(r, 4), 256), (unsigned)ceil_div(n, ZR * ZRB)), dim3(256), 0,
-                     ctx->stream, d_q, s16, n, ld, d_sel, r, d_rm, rinv, mus, sq, rsq, mc32, scale, d_zq, ld_zq, d_colmap,
-                     qmax, d_zb, ld_zb, kbs, d_of);
-  LAUNCHCHK();
+    // an int32 matrix whose rows are not 16-byte aligned
+    hipLaunchKernelGGL(k_zquant4, dim3((unsigned)ceil_div(ceil_div(r, 4), 256), (unsigned)ceil_div(n, ZR * ZRB)),
+                       dim3(256), 0, ctx->stream, d_q, s16, n, ld, d_sel, r, d_rm, rinv, mus, sq, rsq, mc32, scale, d_zq,
+                       ld_zq, d_colmap, qmax, d_zb, ld_zb, kbs, d_of);
+    LAUNCHCHK();
   }
   if (h_overflow) {
     HIPCHK(hipMemcpyAsync(ctx->pinned, d_of, 16, hipMemcpyDeviceToHost, ctx->stream));

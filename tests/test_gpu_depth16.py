@@ -85,31 +85,31 @@ def test_synth_q16_equals_encoded_synth(dev):
     assert torch.equal(d.ecol[:k], ecol) and torch.equal(d.evals[:k], ev)
 
 
-# raw-code software-pipelined column kernels (GRID_COL_PF; 1 or 2 columns per
-# thread, 8 or 16 rows per group) and the streamed row-block kernel
-# (GRID_ROWBLK16_PB=0; GRID_ROWBLK16_WPC=1: one workgroup per CU, many units
-# each); the knobs take effect in the tools build
-# (GRID_AMD_LIB=.../libgridhip_probes.so), the product library runs its defaults
+# selectors of the retired column / row-block variants: no build reads them any
+# more, every set runs the defaults (test_col_stats_pipelined_equal_int32 keeps
+# its cases under them)
 PF_KNOBS = [{"GRID_COL_PF": "0", "GRID_ROWBLK16_PB": "0"}, {"GRID_ROWBLK16_PB": "0", "GRID_ROWBLK16_WPC": "1"},
             {"GRID_ROWBLK16_XOR": "0"}, {"GRID_COL_PF": "1"}, {"GRID_COL_PF": "1", "GRID_COL16_VW": "1"},
             {"GRID_COL_PF": "1", "GRID_COL16_VW": "1", "GRID_COL16_CU": "16"},
             {"GRID_COL_PF": "1", "GRID_COL16_CU": "16"}]
 
 
-@pytest.mark.parametrize("knobs", [{}, {"GRID_COL16_VW": "1", "GRID_ROWBLK16_PB": "1"},
-                                   {"GRID_COL16_VW": "4", "GRID_ROWBLK16_PB": "4", "GRID_ROWBLK_NT": "0",
-                                    "GRID_COL_NT": "0", "GRID_ZQUANT_NT": "0", "GRID_ZQUANT_GROUPS": "3"},
-                                   {"GRID_COL16_CU": "16", "GRID_ROWBLK16_PB": "2", "GRID_ZQUANT_GROUPS": "5"},
-                                   {"GRID_ZQUANT7": "0"}] + PF_KNOBS)
-@pytest.mark.parametrize("pattern", ["every3", "dense"])
-def test_step4_kernels_q16_equal_int32(dev, knobs, pattern, monkeypatch):
-    """Every q16 kernel variant (columns per thread, blocks per workgroup,
-    streaming loads: timing knobs) gives the int32 kernels' bits, including
-    the int16 step-4 codes and their escape list."""
+def step4_both_forms(dev, n, m, pattern, unaligned=False):
+    """Every step-4 kernel on the int32 and on the compact form of one matrix:
+    all outputs equal bit for bit, including the int16 step-4 codes and their
+    escape list.  unaligned: sel and colmap start one int32 past a 16-byte
+    boundary (the compact zquant kernel then takes its 8-byte-load form)."""
     from grid_amd.fused import Depth16, HipOps
-    for k_, v_ in knobs.items():
-        monkeypatch.setenv(k_, v_)
-    n, m = 300, 5 * 8192 + 516          # ld % 4 == 0: the int32 layout of the int16 output
+
+    def place(t):
+        if not unaligned:
+            return t
+        buf = torch.empty(len(t) + 1, dtype=t.dtype, device="cuda")
+        view = buf[1:1 + len(t)]
+        view.copy_(t)
+        assert view.data_ptr() % 16 == 4
+        return view
+
     q = random_depths(n, m, 2)
     q[:, 100] = MISSING
     qd = torch.from_numpy(q).cuda()
@@ -128,8 +128,8 @@ def test_step4_kernels_q16_equal_int32(dev, knobs, pattern, monkeypatch):
         ops.col_means(src, n, m, ld, rm, mu)
         ops.col_vars(src, n, m, ld, rm, mu, var, ratio)
         if pattern == "every3":     # 4 selected columns never share an 8-code window: per-cell gathers
-            sel = torch.arange(0, m, 3, dtype=torch.int32, device="cuda")
-            colmap = torch.arange(len(sel), dtype=torch.int32, device="cuda")
+            sel = place(torch.arange(0, m, 3, dtype=torch.int32, device="cuda"))
+            colmap = place(torch.arange(len(sel), dtype=torch.int32, device="cuda"))
         else:                       # ~90 % selected, r % 4 != 0, panel holes (colmap -1) and runs
             keep = np.random.default_rng(5).random(m) < 0.9
             keep[-3:] = [True, False, True]
@@ -138,8 +138,8 @@ def test_step4_kernels_q16_equal_int32(dev, knobs, pattern, monkeypatch):
                 sel_np = sel_np[:-1]
             hole = np.random.default_rng(6).random(len(sel_np)) < 0.05
             cm_np = np.where(hole, -1, np.cumsum(~hole) - 1).astype(np.int32)
-            sel = torch.from_numpy(sel_np).cuda()
-            colmap = torch.from_numpy(cm_np).cuda()
+            sel = place(torch.from_numpy(sel_np).cuda())
+            colmap = place(torch.from_numpy(cm_np).cuda())
         r = len(sel)
         zq = torch.zeros((n, r), dtype=torch.int32, device="cuda")
         kp = -(-r // 64) * 64
@@ -156,6 +156,34 @@ def test_step4_kernels_q16_equal_int32(dev, knobs, pattern, monkeypatch):
         out[name] = [t.cpu().numpy() for t in (bsum, bcnt, rm, mu, var, ratio, zq, zb, zq16, zb16) + esc]
     for a, b in zip(out["i32"], out["q16"]):
         assert np.array_equal(a, b, equal_nan=True)
+
+
+@pytest.mark.parametrize("knobs", [{}, {"GRID_ROWBLK_NT": "0", "GRID_COL_NT": "0", "GRID_ZQUANT_NT": "0",
+                                        "GRID_ZQUANT_GROUPS": "3"},
+                                   {"GRID_ZQUANT_GROUPS": "5"}, {"GRID_ZQUANT_NT": "1"}, {"GRID_ZQUANT_NT": "0"}])
+@pytest.mark.parametrize("pattern", ["every3", "dense"])
+def test_step4_kernels_q16_equal_int32(dev, knobs, pattern, monkeypatch):
+    """Every q16 kernel under the performance knobs (streaming or plain loads,
+    row groups per workgroup; GRID_ZQUANT_NT=1: the streaming compact zquant
+    kernel; GRID_ZQUANT_NT=0 alone: the source-column zquant kernels with
+    plain loads at one row group per workgroup) gives the int32 kernels'
+    bits, including the int16 step-4 codes and their escape list."""
+    for k_, v_ in knobs.items():
+        monkeypatch.setenv(k_, v_)
+    step4_both_forms(dev, 300, 5 * 8192 + 516, pattern)   # ld % 4 == 0: the int32 layout of the int16 output
+
+
+@pytest.mark.parametrize("knobs", [{}, {"GRID_ZQUANT_NT": "1"}])
+@pytest.mark.parametrize("pattern", ["every3", "dense"])
+def test_step4_zquant_8byte_loads_equal_int32(dev, knobs, pattern, monkeypatch):
+    """sel and colmap not 16-byte aligned: the compact zquant kernel's
+    8-byte-load form, with plain (default) and streaming (GRID_ZQUANT_NT=1)
+    loads.  13 rows (one full group of 8 and a ragged one), more than 1,024
+    selected columns (two column blocks), r % 4 != 0, panel holes and
+    per-cell gathers."""
+    for k_, v_ in knobs.items():
+        monkeypatch.setenv(k_, v_)
+    step4_both_forms(dev, 13, 8192 + 516, pattern, unaligned=True)
 
 
 def test_chain_q16_equals_int32(dev):

@@ -29,7 +29,7 @@ ap.add_argument("--q16", action="store_true", help="compact depth matrix (grid_d
 ap.add_argument("--groups", default="1", help="comma list of GRID_ZQUANT_GROUPS values to time")
 ap.add_argument("--ldz-align", type=int, default=8, help="step-4 output row stride rounded up to this many columns")
 ap.add_argument("--env", default="", help="semicolon list of K=V[,K=V] settings to time full16 under "
-                "(the tools build's probes, e.g. GRID_Z7_PROBE=3)")
+                "(e.g. GRID_ZQUANT_NT=1: streaming loads)")
 a = ap.parse_args()
 
 
