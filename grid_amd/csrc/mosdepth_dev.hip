@@ -17,9 +17,11 @@
 //
 // Kernels per batch of files: k_md_count (newlines per 16 KiB chunk, any
 // byte >= 0x80), k_md_scan (per-file prefix of the chunk counts), k_md_parse
-// (one workgroup per chunk: the chunk in LDS, one thread per 256-byte
+// (one workgroup per chunk: the chunk in LDS, one thread per 64-byte
 // segment, each line parsed by the thread whose segment holds its first
-// byte, its index from a block scan of the newline counts).
+// byte, its index from a block scan of the newline counts).  A line of more
+// than MAXLINE = 256 bytes, whether or not it passes the prefix test or ends
+// in a newline, is outside the grammar (GRID_MD_EXOTIC).
 #include "common.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -77,6 +79,12 @@ __device__ __forceinline__ bool md_masked(const MdOpts &o, P c, int clen, int64_
   return false;
 }
 
+// bit 7 of every byte of w that is '\n', exact per byte (no carry crosses a byte)
+__device__ __forceinline__ uint32_t nl_bits(uint32_t w) {
+  const uint32_t x = w ^ 0x0A0A0A0Au;                               // '\n' -> 0
+  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+}
+
 // newlines per chunk; any byte >= 0x80 in a file -> flags |= GRID_MD_EXOTIC
 __global__ __launch_bounds__(256) void k_md_count(const uint8_t *__restrict__ text, const int64_t *__restrict__ toff,
                                                   const int64_t *__restrict__ tlen, const int32_t *__restrict__ cfile,
@@ -90,13 +98,12 @@ __global__ __launch_bounds__(256) void k_md_count(const uint8_t *__restrict__ te
   for (int64_t i = a + threadIdx.x * 16; i < b; i += 256 * 16) {
     if (i + 16 <= b) {
       const uint4 v = *reinterpret_cast<const uint4 *>(t + i);
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const uint32_t x = w[k] ^ 0x0A0A0A0Au;            // bytes equal to '\n' become 0
-        n += __builtin_popcount(((x - 0x01010101u) & ~x & 0x80808080u));
-        hi |= (w[k] & 0x80808080u) != 0;
-      }
+      // the parse's own per-byte test (nl_bits): its line numbers are this count
+      // continued.  The borrow form (x - 0x01010101) & ~x & 0x80808080 tells
+      // whether a word HAS a '\n' but counts a 0x0B behind one as another
+      n += __builtin_popcount(nl_bits(v.x)) + __builtin_popcount(nl_bits(v.y)) + __builtin_popcount(nl_bits(v.z)) +
+           __builtin_popcount(nl_bits(v.w));
+      hi |= ((v.x | v.y | v.z | v.w) & 0x80808080u) != 0;
     } else {
       for (int64_t j = i; j < b; j++) {
         n += t[j] == '\n';
@@ -199,8 +206,7 @@ __device__ __forceinline__ uint32_t nl_mask16(const uint4 v) {
   uint32_t m = 0;
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    const uint32_t x = w[k] ^ 0x0A0A0A0Au;                          // '\n' -> 0
-    const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);   // bit 7 of each zero byte
+    const uint32_t z = nl_bits(w[k]);
     m |= (((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u)) << (4 * k);
   }
   return m;
@@ -233,10 +239,10 @@ __device__ __forceinline__ int32_t md_tag(int64_t idx) { return (int32_t)(GRID_M
 // lines as MODE 1 in two launches over the same text, 2 the tag pass (counts
 // nothing), 3 the resolve pass (kept[f] += 1 per cell it fills).
 //
-// One workgroup per 64 KiB chunk: the chunk (and 16 bytes before it, up to
+// One workgroup per 16 KiB chunk: the chunk (and 16 bytes before it, up to
 // MAXLINE after it) is loaded into LDS with 16-byte loads all in flight; each
-// thread owns a 256-byte segment and parses the lines that START in it, found
-// from the newline bit masks of its 16 words; line numbers come from a block
+// thread owns a 64-byte segment and parses the lines that START in it, found
+// from the newline bit masks of its 4 words; line numbers come from a block
 // scan of the per-segment newline counts.
 // waves per SIMD the parse is held to, and 16-B loads in flight per thread
 // while the chunk fills LDS: 8 / 3 fit 62 VGPRs without spills and 8
@@ -415,7 +421,9 @@ __global__ __launch_bounds__(PTH) __attribute__((amdgpu_waves_per_eu(GRID_MDPARS
       const int64_t lim = min(L, cur + MAXLINE + 1) - cur;
       int len = 0;
       while (len < lim && p[len] != '\n') len++;
-      if (len == lim && cur + len < L) bad |= GRID_MD_EXOTIC;    // longer than MAXLINE
+      // longer than MAXLINE: the file's unterminated last line too (len == lim
+      // <= MAXLINE is that line ending with the file)
+      if (len > MAXLINE) bad |= GRID_MD_EXOTIC;
       else line(cur, len, idx);
     }
   }

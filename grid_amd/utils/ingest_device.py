@@ -14,7 +14,7 @@ model whose rates are re-measured every batch (``_Split``):
   * CPU (grid_gunzip_host: libdeflate, zlib without it): threads inflate
     whole files into pinned staging, copied to HBM on a second stream while
     the GPU works.
-The text then is cut in 64 KiB chunks and parsed on the GPU (grid_md_count /
+The text then is cut in 16 KiB chunks and parsed on the GPU (grid_md_count /
 grid_md_parse_map: the reference's line filters, each record placed by its
 (start, end) in the key list K of the reference file).  Then the population
 means in file order, the valid columns, the empty-sample filter and the rows
@@ -40,7 +40,11 @@ no memory beyond the matrix).  normalize_mosdepth.ingest tries strict first and
 general on DeviceIngestKeys (config ``mosdepth.normalize.device_keys``).
 
 What still hands over in either mode -- a line outside the canonical mosdepth
-grammar or a non-ASCII byte, a key outside K, text in HBM that does not match
+grammar or a non-ASCII byte, a line of more than 256 bytes (mosdepth_dev.hip
+MAXLINE: the look-ahead a parse chunk holds; it applies to every line, one
+that fails the chromosome prefix and the file's unterminated last line
+included), with no chromosome prefix an empty line (the reference skips it,
+the device grammar has no such line), a key outside K, text in HBM that does not match
 its gzip CRC, a file of plain gzip members whose total size its trailer does
 not give, a reference file that keeps no record; in strict mode reference keys
 that are not strictly increasing or a repeated key (DeviceIngestKeys); in
@@ -326,7 +330,7 @@ class _Async:
     the GPU; after the first batch, which builds the key list K synchronously).
     Per batch, with no host round trip:
       copy stream:  [wait: batch b-2's parse done] compressed input + the batch's
-                    tables (member units, files, 64 KiB chunks: one pinned arena)
+                    tables (member units, files, 16 KiB chunks: one pinned arena)
                     -> HBM (d_in / tables of parity b % 2); event h2d[b % 2];
       main stream:  [wait h2d] grid_gunzip_batch (inflate + CRC) -> grid_file_status
                     (files with a failed member are skipped by the parse, as the

@@ -56,7 +56,7 @@ def split(request, monkeypatch):
     return request.param
 
 
-def _dev_vs_host(dev, d, samples, chrom=None, start=None, end=None, excluded=None, lo=20, hi=100):
+def _dev_vs_host(dev, d, samples, chrom=None, start=None, end=None, excluded=None, lo=20, hi=100, keys="strict"):
     # the file order is the caller's sample order, not the directory's glob
     # order: the device path takes the first batch's largest file as its key
     # list, and a later file with a key outside it hands the cohort to the host
@@ -66,7 +66,7 @@ def _dev_vs_host(dev, d, samples, chrom=None, start=None, end=None, excluded=Non
     m = nm.map_mosdepth_files_to_samples(d, samples)
     inds = {s: m[s] for s in samples if s in m}
     ex = excluded or {}
-    a = nm._ingest_dev(dev, inds, d, chrom, start, end, ex, lo, hi, 4)
+    a = nm._ingest_dev(dev, inds, d, chrom, start, end, ex, lo, hi, 4, keys=keys)
     b = nm.ingest_native(inds, d, chrom, start, end, ex, lo, hi, 4)
     assert a[0] == b[0], (a[0], b[0])
     assert a[1] == b[1]
