@@ -161,6 +161,8 @@ _SIGS = {
     "grid_ctx_own_stream_cumask": [_vp, _vp, _i32],
     "grid_ctx_stream": [_vp, C.POINTER(_vp)],
     "grid_knn_seg_pack": [_vp, _vp, _i64, _i64, _i64, _vp],
+    "grid_knn_seg_tiles_pack": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],
+    "grid_knn_seg_rows_fill": [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64],
     # distributed `grid wgs` (grid_amd/utils/dist_step4.py)
     "grid_md_popsum": [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp],
     "grid_md_popvalid": [_vp, _vp, _vp, _i64, _f64, _f64, _vp],

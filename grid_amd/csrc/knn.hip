@@ -1696,6 +1696,61 @@ __global__ __launch_bounds__(256) void k_seg_pack(const int64_t *__restrict__ gr
   }
 }
 
+// ---- complete rows from the segments (k + 1 > GRID_SEG_K1) -------------------
+// Row block b lacks columns [0, b B): for b' < b that part is the transposed
+// tile T(b', b)[u][c] = seg_b'[c][(b - b') B + u], held by rank own(b').  THE
+// exchange rule (include/grid_abi.h): rank own(b') sends T(b', b) to rank
+// own(b) in this slot of the pair's two.  With p = own(b'), q = own(b):
+// p < q carries T(p, q) and T(p, 2W-1-q), p > q carries T(p, 2W-1-q) and
+// T(2W-1-p, 2W-1-q), p = q only T(p, 2W-1-p).
+__host__ __device__ __forceinline__ int64_t seg_own(int64_t b, int64_t W) { return b < W ? b : 2 * W - 1 - b; }
+__host__ __device__ __forceinline__ int64_t seg_tile_slot(int64_t bs, int64_t b, int64_t W) {
+  const int64_t p = seg_own(bs, W), q = seg_own(b, W);
+  if (p < q) return b < W ? 0 : 1;
+  if (p > q) return bs < W ? 0 : 1;
+  return 0;
+}
+
+// One 32x32 int64 sub-tile per workgroup through LDS: blockIdx.z = tile
+// (b = bs + 1 + z), blockIdx.x / .y = the sub-tile's u / c origin.  Reads run
+// along segment rows and writes along tile rows (256-B runs both); the LDS
+// rows are padded by one 8-byte element, so the 16-lane write groups fill 32
+// distinct banks and the 32-lane transposed reads 64.  Cells beyond B (the
+// last sub-tile in each direction) are neither read nor written.
+__global__ __launch_bounds__(256) void k_seg_tiles_pack(const int64_t *__restrict__ seg, int64_t ld, int64_t B,
+                                                        int64_t W, int64_t bs, int64_t *__restrict__ send) {
+  __shared__ int64_t t[32][33];
+  const int64_t b = bs + 1 + blockIdx.z;
+  const int64_t u0 = (int64_t)blockIdx.x * 32, c0 = (int64_t)blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int64_t *src = seg + (b - bs) * B;
+#pragma unroll
+  for (int r = ty; r < 32; r += 8) {
+    const int64_t c = c0 + r, u = u0 + tx;
+    if (c < B && u < B) t[r][tx] = src[c * ld + u];
+  }
+  __syncthreads();
+  int64_t *dst = send + (2 * seg_own(b, W) + seg_tile_slot(bs, b, W)) * B * B;
+#pragma unroll
+  for (int r = ty; r < 32; r += 8) {
+    const int64_t u = u0 + r, c = c0 + tx;
+    if (u < B && c < B) dst[u * B + c] = t[tx][r];
+  }
+}
+
+// blockIdx.x = row u of block b, blockIdx.y = column block b': one coalesced
+// copy of B cells, from the received tile T(b', b) for b' < b, else from the
+// block's own segment
+__global__ __launch_bounds__(256) void k_seg_rows_fill(const int64_t *__restrict__ seg, int64_t ld,
+                                                       const int64_t *__restrict__ recv, int64_t B, int64_t W,
+                                                       int64_t b, int64_t *__restrict__ rows, int64_t ld_rows) {
+  const int64_t u = blockIdx.x, bs = blockIdx.y;
+  const int64_t *src = bs < b ? recv + ((2 * seg_own(bs, W) + seg_tile_slot(bs, b, W)) * B + u) * B
+                              : seg + u * ld + (bs - b) * B;
+  int64_t *dst = rows + u * ld_rows + bs * B;
+  for (int64_t c = threadIdx.x; c < B; c += blockDim.x) dst[c] = src[c];
+}
+
 // Row top-(k+1) for larger k: 8-pass radix select on the packed keys over the
 // (coalesced) row, then a bitonic sort of the <= SELCAP survivors.
 constexpr int SELCAP = 4096;
@@ -2487,6 +2542,36 @@ int grid_knn_seg_pack(grid_ctx *ctx, const int64_t *d_gram, int64_t np_, int64_t
           "bad args");
   hipLaunchKernelGGL(k_seg_pack, dim3((unsigned)B, (unsigned)(2 * W)), dim3(256), 0, ctx->stream, d_gram, np_, W, B,
                      d_send);
+  LAUNCHCHK();
+  return GRID_OK;
+}
+
+int grid_knn_seg_tiles_pack(grid_ctx *ctx, const int64_t *d_seg, int64_t ld, int64_t B, int64_t W, int64_t b_src,
+                            int64_t *d_send) {
+  REQUIRE(ctx && d_seg && d_send, "bad args");
+  REQUIRE(W > 0 && W <= 32768 && B > 0 && B <= (1 << 20), "bad W / B (W <= 32768, B <= 2^20)");
+  REQUIRE(b_src >= 0 && b_src < 2 * W, "block %lld outside [0, 2W)", (long long)b_src);
+  REQUIRE(ld >= (2 * W - b_src) * B, "ld (%lld) below the segment width %lld", (long long)ld,
+          (long long)((2 * W - b_src) * B));
+  const int64_t tiles = 2 * W - 1 - b_src, sub = ceil_div(B, 32);
+  if (tiles == 0) return GRID_OK;            // the last block sends nothing
+  hipLaunchKernelGGL(k_seg_tiles_pack, dim3((unsigned)sub, (unsigned)sub, (unsigned)tiles), dim3(256), 0, ctx->stream,
+                     d_seg, ld, B, W, b_src, d_send);
+  LAUNCHCHK();
+  return GRID_OK;
+}
+
+int grid_knn_seg_rows_fill(grid_ctx *ctx, const int64_t *d_seg, int64_t ld, const int64_t *d_recv, int64_t B,
+                           int64_t W, int64_t b, int64_t *d_rows, int64_t ld_rows) {
+  REQUIRE(ctx && d_seg && d_recv && d_rows, "bad args");
+  REQUIRE(W > 0 && W <= 32768 && B > 0 && B <= (1 << 20), "bad W / B (W <= 32768, B <= 2^20)");
+  REQUIRE(b >= 0 && b < 2 * W, "block %lld outside [0, 2W)", (long long)b);
+  REQUIRE(ld >= (2 * W - b) * B, "ld (%lld) below the segment width %lld", (long long)ld,
+          (long long)((2 * W - b) * B));
+  REQUIRE(ld_rows >= 2 * W * B, "ld_rows (%lld) below the row width %lld", (long long)ld_rows,
+          (long long)(2 * W * B));
+  hipLaunchKernelGGL(k_seg_rows_fill, dim3((unsigned)B, (unsigned)(2 * W)), dim3(256), 0, ctx->stream, d_seg, ld,
+                     d_recv, B, W, b, d_rows, ld_rows);
   LAUNCHCHK();
   return GRID_OK;
 }

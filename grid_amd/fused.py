@@ -34,6 +34,9 @@ Multi-GPU: the bin (column) axis is sharded in 8192-aligned ranges
   * every pair lies in one segment (as a row or as a column entry), so the
     per-segment row and column candidates (k+1 each), all-gathered, give
     every rank the exact neighbour lists of all rows (grid_knn_seg_merge);
+    above the lists' 16 keys (k + 1 > 16) the segments' transposed tiles move
+    in one all-to-all instead, each rank selects from the complete rows of its
+    own two blocks, and the lists are all-gathered (Steps47._seg_rows);
     dipCN and phasing are replicated (tiny / sequential per locus).
 
 The chain is written against an ``ops`` object.  The product always uses
@@ -278,6 +281,15 @@ class SimComm:
         out.view(-1).copy_(t.view(self.world, -1)[self.rank])
         return out
 
+    def all_to_all(self, out, inp, out_splits, in_splits):
+        """The local block's copy; the other W - 1 blocks are what the real
+        all-to-all brings in ((W-1)/W of the bytes at equal splits)."""
+        r, es = self.rank, out.element_size()
+        self._count("all_to_all", (sum(int(x) for x in out_splits) - int(out_splits[r])) * es)
+        o0, i0 = sum(int(x) for x in out_splits[:r]), sum(int(x) for x in in_splits[:r])
+        out.reshape(-1)[o0:o0 + int(out_splits[r])].copy_(inp.reshape(-1)[i0:i0 + int(in_splits[r])])
+        return out
+
     def all_gather_into(self, out, t, async_op=False):
         """The W copies; with async_op on a side stream ordered after the work
         queued so far (as RCCL's stream is), the handle's wait() orders the
@@ -452,6 +464,14 @@ class HipOps:
     def seg_merge(self, rowc, colc, ldc, B, n, k, idx, d2, cnt):
         call("grid_knn_seg_merge", self.ctx, ptr(rowc), ptr(colc), ldc, B, n, k, ptr(idx), ptr(d2), ptr(cnt))
 
+    def seg_tiles_pack(self, seg, ld, B, W, b_src, send):
+        """Every transposed tile of segment b_src into send [W][2][B][B]."""
+        call("grid_knn_seg_tiles_pack", self.ctx, ptr(seg), ld, B, W, b_src, ptr(send))
+
+    def seg_rows_fill(self, seg, ld, recv, B, W, b, rows, ld_rows):
+        """Block b's complete rows [B][ld_rows] from its segment and recv [W][2][B][B]."""
+        call("grid_knn_seg_rows_fill", self.ctx, ptr(seg), ld, ptr(recv), B, W, b, ptr(rows), ld_rows)
+
     def topk_rows(self, rows, ld, norms, n, k, row0, nrows, idx, d2, cnt):
         call("grid_knn_topk_rows", self.ctx, ptr(rows), ld, ptr(norms), n, k, row0, nrows, ptr(idx), ptr(d2),
              ptr(cnt))
@@ -532,7 +552,8 @@ class Steps47:
 
     def __init__(self, ops, alloc, n, m_total, col0, m_local, *, k=10, n_nbr=300, top_frac=0.1, zmax=2.0,
                  sigma2_max=1000.0, frac_r=1.0, min_nbr=1, n_iters=100, comm=None, phase_lane=None, zq16=True,
-                 chunk=None, keep_z=True, on_z_chunk=None, split="bin", piece_bytes=1 << 31, col_lane=None):
+                 chunk=None, keep_z=True, on_z_chunk=None, split="bin", piece_bytes=1 << 31, col_lane=None,
+                 step5_wide="auto"):
         """``phase_lane``: optional (ops, torch.cuda.Stream) pair on which step
         7 runs.  Phasing is one workgroup for ~4 ms, so on its own stream it
         overlaps other work instead of idling the other 255 CUs.  It is
@@ -555,7 +576,16 @@ class Steps47:
         an all-gather overlapped with the Gram of the previous piece, and
         every rank computes its own two row segments over ALL bins -- no
         Gram reduce-scatter.  Both give the same segments, bit for bit
-        (integer sums), and share the candidate merge."""
+        (integer sums), and share the candidate merge.
+
+        ``step5_wide`` (multi-rank runs with k + 1 above the candidate lists'
+        16 keys): "auto" exchanges the segments' transposed tiles so that
+        every rank selects its own two row blocks from complete rows
+        (``row_exchange``, both splits; ops without the two tile operations
+        keep the earlier routes); "allreduce" (bin split only) forces the
+        earlier route, the all-reduce of the whole Gram (``full_rows``)."""
+        if step5_wide not in ("auto", "allreduce"):
+            raise ValueError(f"step5_wide must be 'auto' or 'allreduce', not {step5_wide!r}")
         self.ops, self.A, self.comm = ops, alloc, comm
         # col_lane: optional (ops, torch stream) pair for the column-statistics
         # passes of a one-chunk shard -- a stream CU-masked away from the phase
@@ -573,6 +603,8 @@ class Steps47:
         if split not in ("bin", "cohort"):
             raise ValueError(f"split must be 'bin' or 'cohort', not {split!r}")
         self.split = split if comm is not None else "bin"
+        if step5_wide == "allreduce" and self.split != "bin":
+            raise ValueError("step5_wide='allreduce' is a bin-split route")
         self.n, self.m, self.col0, self.ml = n, m_total, col0, m_local
         assert col0 % BLOCK == 0
         self.k, self.n_nbr, self.top_frac = k, n_nbr, top_frac
@@ -651,10 +683,17 @@ class Steps47:
         self.norms.zero_()
         kk = max(k, 1)
         # k + 1 above the segment candidate lists' length (the drop-in's
-        # num_neighbors may be the reference's default 500): the bin split then
-        # sums the whole upper triangle over the ranks (one all-reduce of the
-        # np x np int64 Gram) and every rank selects from whole rows
-        self.full_rows = comm is not None and kk + 1 > _abi.SEG_K1
+        # num_neighbors may be the reference's default 500).  row_exchange: the
+        # segments' transposed tiles travel in one all-to-all (2 B^2 int64 per
+        # rank pair, whatever k is) and every rank selects its own two row
+        # blocks from complete rows (_seg_rows).  full_rows (ops without the
+        # tile operations, or step5_wide="allreduce"): the bin split sums the
+        # whole upper triangle over the ranks (one all-reduce of the np x np
+        # int64 Gram) and every rank selects from all n whole rows
+        wide = comm is not None and kk + 1 > _abi.SEG_K1
+        self.row_exchange = (wide and step5_wide == "auto" and hasattr(ops, "seg_tiles_pack")
+                             and hasattr(ops, "seg_rows_fill"))
+        self.full_rows = wide and not self.row_exchange
         if self.full_rows and self.split != "bin":
             raise _abi.GridNativeError(f"the cohort split needs k + 1 <= {_abi.SEG_K1}")
         if comm is not None and not self.full_rows:
@@ -672,9 +711,24 @@ class Steps47:
                 self.piece = max(2, min(nkb, int(piece_bytes // per_blk)) // 2 * 2)
                 self.gbuf = [a.empty((W * self.piece, self.np_, _abi.KBW), U2) for _ in range(2)]
                 self.norms_l = a.empty((2, B), I8)
-            K1 = _abi.SEG_K1
-            self.rowc_l = a.empty((2, B, K1), I8)               # packed keys (uint64 bits)
-            self.colc_l = a.empty((2, self.npw, K1), I8)
+            if self.row_exchange:
+                # tiles out / in [W][2][B][B] (the pair p -> p fills one slot:
+                # zeroed once, so no collective moves unwritten memory), this
+                # rank's complete rows, and its blocks' lists; rows >= n keep
+                # (-1, 0, 0), which the selection never writes
+                self.x_send, self.x_recv = a.empty((W, 2, B, B), I8), a.empty((W, 2, B, B), I8)
+                self.x_send.zero_()
+                self.x_recv.zero_()
+                self.rows_l = a.empty((2, B, self.npw), I8)
+                self.bidx_l, self.bd2_l = a.empty((2, B, kk), I4), a.empty((2, B, kk), I8)
+                self.bcnt_l = a.empty((2, B), I4)
+                self.bidx_l.fill_(-1)
+                self.bd2_l.zero_()
+                self.bcnt_l.zero_()
+            else:
+                K1 = _abi.SEG_K1
+                self.rowc_l = a.empty((2, B, K1), I8)               # packed keys (uint64 bits)
+                self.colc_l = a.empty((2, self.npw, K1), I8)
             # gathered lists -> global block order: block b is rank b (slot 0)
             # for b < W, else rank 2W-1-b (slot 1)
             self.blk_src = [(b, 0) if b < W else (2 * W - 1 - b, 1) for b in range(2 * W)]
@@ -968,23 +1022,7 @@ class Steps47:
         # the previous pass's deferred phasing starts once this pass's Gram is done
         if not profile:
             self._issue_pending()
-        # ---- step 5: full rows (mirror), reduce-scatter by row blocks, top-k ----
-        if self.split == "cohort":
-            self._step5_cohort()
-        elif self.full_rows:
-            self.comm.all_reduce_sum(self.gram[: self.np_])
-            o.mirror(self.gram, self.np_)
-            o.diag(self.gram, self.np_, n, self.norms)
-            o.topk_rows(self.gram, self.np_, self.norms, n, self.k, 0, n, self.idx_l, self.d2_l, self.cnt_l)
-        elif self.comm is not None:
-            o.mirror(self.gram, self.np_)
-            o.diag(self.gram, self.np_, n, self.norms)
-            self.comm.all_reduce_sum(self.norms)
-            self._step5_segments()
-        else:
-            o.mirror(self.gram, self.np_)
-            o.diag(self.gram, self.np_, n, self.norms)
-            o.topk_rows(self.gram, self.np_, self.norms, n, self.k, 0, n, self.idx_l, self.d2_l, self.cnt_l)
+        self._step5()
         idx, self.d2, cnt = self.idx_l, self.d2_l, self.cnt_l
         self._mark("topk")
         if upto == "step5":
@@ -1045,18 +1083,42 @@ class Steps47:
         if ddef is not None and int(h[2]) & 0xFFFFFFFF:
             raise ZeroDivisionError("float division by zero")
 
+    def _step5(self):
+        """Step 5's tail, from the accumulated Gram (the cohort split: from
+        this rank's two segments) to the neighbour lists idx_l / d2_l / cnt_l:
+        full rows (mirror), reduce-scatter by row blocks, top-k."""
+        o, n = self.ops, self.n
+        if self.split == "cohort":
+            self._step5_cohort()
+        elif self.full_rows:
+            self.comm.all_reduce_sum(self.gram[: self.np_])
+            o.mirror(self.gram, self.np_)
+            o.diag(self.gram, self.np_, n, self.norms)
+            o.topk_rows(self.gram, self.np_, self.norms, n, self.k, 0, n, self.idx_l, self.d2_l, self.cnt_l)
+        elif self.comm is not None:
+            o.mirror(self.gram, self.np_)
+            o.diag(self.gram, self.np_, n, self.norms)
+            self.comm.all_reduce_sum(self.norms)
+            self._step5_segments()
+        else:
+            o.mirror(self.gram, self.np_)
+            o.diag(self.gram, self.np_, n, self.norms)
+            o.topk_rows(self.gram, self.np_, self.norms, n, self.k, 0, n, self.idx_l, self.d2_l, self.cnt_l)
+
     def _step5_segments(self):
         """Sharded step 5: reduce-scatter the upper-triangle segments (each
         rank sends W segment pairs, receives its own two, summed over ranks),
-        row and column candidates per segment, an all-gather of the candidate
-        lists, and the exact merge into every row's neighbours on every rank
-        (grid_knn_seg_topk / grid_knn_seg_merge)."""
+        then, for k + 1 <= 16, row and column candidates per segment, an
+        all-gather of the candidate lists, and the exact merge into every
+        row's neighbours on every rank (grid_knn_seg_topk /
+        grid_knn_seg_merge); above that, the row exchange (_seg_rows)."""
         o, n, W, B, npw, np_ = self.ops, self.n, self.world, self.B, self.npw, self.np_
+        tail = self._seg_rows if self.row_exchange else self._seg_candidates
         if hasattr(o, "seg_pack"):
             o.seg_pack(self.gram, np_, W, B, self.seg_send)
             self.comm.reduce_scatter_sum(self.seg_recv, self.seg_send)
             self._mark("reduce_scatter")
-            self._seg_candidates()
+            tail()
             return
         send = self.seg_send.view(W, self.seg_len)
         for q in range(W):                       # rank q's slot: its blocks q and 2W-1-q
@@ -1075,7 +1137,7 @@ class Steps47:
                 off += B * nc
         self.comm.reduce_scatter_sum(self.seg_recv, self.seg_send)
         self._mark("reduce_scatter")
-        self._seg_candidates()
+        tail()
 
     def _cohort_plan(self, kb):
         """The cohort split's exchange rounds: per chunk index, the most
@@ -1156,7 +1218,45 @@ class Steps47:
         sel_s = torch.tensor([s_ for _, s_ in self.blk_src], device=ng.device)
         self.norms.copy_(ng[sel_q, sel_s].reshape(-1)[:np_])
         self._mark("gram_rows")
-        self._seg_candidates()
+        if self.row_exchange:
+            self._seg_rows()
+        else:
+            self._seg_candidates()
+
+    def _seg_rows(self):
+        """k + 1 above the candidate lists: complete rows instead.  Row block
+        b's segment lacks columns [0, b B), which are transposed tiles of the
+        segments b' < b (include/grid_abi.h states the exchange rule): pack
+        this rank's two segments' tiles, one all-to-all of 2 B^2 int64 per
+        rank pair, fill this rank's two row blocks, select from them with the
+        row kernels, all-gather the lists and order them by global row.  Every
+        rank issues the same collectives, whatever its blocks hold."""
+        o, n, W, B, npw = self.ops, self.n, self.world, self.B, self.npw
+        torch = self.A.torch
+        kk, n1 = max(self.k, 1), max(n, 1)
+        segs, off = [], 0
+        for b in self.my_blocks:
+            nc = (2 * W - b) * B
+            segs.append((b, self.seg_recv[off:off + B * nc], nc))
+            off += B * nc
+        for b, seg, nc in segs:
+            o.seg_tiles_pack(seg, nc, B, W, b, self.x_send)
+        self.comm.all_to_all(self.x_recv, self.x_send, [2 * B * B] * W, [2 * B * B] * W)
+        self._mark("row_exchange")
+        for slot, (b, seg, nc) in enumerate(segs):
+            o.seg_rows_fill(seg, nc, self.x_recv, B, W, b, self.rows_l[slot], npw)
+            nr = min(max(n - b * B, 0), B)
+            if nr:                                      # a padding block's lists keep (-1, 0, 0)
+                o.topk_rows(self.rows_l[slot], npw, self.norms, n, self.k, b * B, nr, self.bidx_l[slot],
+                            self.bd2_l[slot], self.bcnt_l[slot])
+        ig = self.comm.all_gather(self.bidx_l)              # [W][2][B][k]
+        dg = self.comm.all_gather(self.bd2_l)
+        cg = self.comm.all_gather(self.bcnt_l)              # [W][2][B]
+        sel_q = torch.tensor([q for q, _ in self.blk_src], device=ig.device)
+        sel_s = torch.tensor([s_ for _, s_ in self.blk_src], device=ig.device)
+        self.idx_l.copy_(ig[sel_q, sel_s].reshape(-1, kk)[:n1])     # [2W][B][k] = global row order
+        self.d2_l.copy_(dg[sel_q, sel_s].reshape(-1, kk)[:n1])
+        self.cnt_l.copy_(cg[sel_q, sel_s].reshape(-1)[:n1])
 
     def _seg_candidates(self):
         """Row and column candidates of this rank's two (complete) segments,

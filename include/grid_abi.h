@@ -409,6 +409,23 @@ int grid_knn_seg_pack(grid_ctx *ctx, const int64_t *d_gram, int64_t np_, int64_t
 int grid_knn_seg_merge(grid_ctx *ctx, const unsigned long long *d_rowc, const unsigned long long *d_colc,
                        int64_t ldc, int64_t B, int64_t n, int64_t k, int32_t *d_idx, int64_t *d_d2,
                        int32_t *d_cnt);
+/* k + 1 > GRID_SEG_K1: complete rows from the segments instead of candidates.
+ * own(b) = b < W ? b : 2W-1-b holds segment b ([B][ld], ld >= (2W - b) B, its
+ * diagonal block mirrored).  Row block b lacks columns [0, b B): for b' < b
+ * that part is the transposed tile T(b', b)[u][c] = seg_b'[c][(b - b') B + u]
+ * (u, c < B).  One all-to-all of equal splits moves them: send and receive
+ * buffers are [W][2][B][B] int64, and the pair p = own(b') -> q = own(b)
+ * carries, in slots 0 and 1,
+ *   p < q: T(p, q), T(p, 2W-1-q);   p > q: T(p, 2W-1-q), T(2W-1-p, 2W-1-q);
+ *   p = q: T(p, 2W-1-p) in slot 0 (slot 1 is never written nor read).
+ * grid_knn_seg_tiles_pack: every tile T(b_src, b), b_src < b < 2W, of segment
+ * b_src into d_send[own(b)][slot].  grid_knn_seg_rows_fill: the complete rows
+ * of block b, d_rows [B][ld_rows] (ld_rows >= 2 W B): columns [b B, 2 W B)
+ * from the segment, columns of block b' < b from d_recv[own(b')][slot]. */
+int grid_knn_seg_tiles_pack(grid_ctx *ctx, const int64_t *d_seg, int64_t ld, int64_t B, int64_t W, int64_t b_src,
+                            int64_t *d_send);
+int grid_knn_seg_rows_fill(grid_ctx *ctx, const int64_t *d_seg, int64_t ld, const int64_t *d_recv, int64_t B,
+                           int64_t W, int64_t b, int64_t *d_rows, int64_t ld_rows);
 
 /* ---------------------------------------------------- step 6: diploid CN
  * Replaces grid/utils/compute_dipcn.py :62-88.
