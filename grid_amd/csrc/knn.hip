@@ -42,37 +42,7 @@ __device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// Upper-triangle tile t -> (ti, tj) in SUPER-BLOCK order: 8x8 groups of
-// 128-tiles are enumerated one after another (triangle of groups, then the
-// tiles of a group row-major), so the ~64 workgroups an XCD runs at once share
-// 8 A and 8 B row panels in its L2 instead of 1 A and 64 B panels.
-constexpr int SBK = 8;
-__device__ __forceinline__ void tile_blocked(int t, int nt, int &ti, int &tj) {
-  const int nb = (nt + SBK - 1) / SBK;
-  for (int bi = 0; bi < nb; bi++) {
-    const int hi = min(SBK, nt - bi * SBK);
-    for (int bj = bi; bj < nb; bj++) {
-      const int hj = min(SBK, nt - bj * SBK);
-      const int cnt = bi == bj ? hi * (hi + 1) / 2 : hi * hj;
-      if (t < cnt) {
-        if (bi != bj) {
-          ti = bi * SBK + t / hj;
-          tj = bj * SBK + t % hj;
-        } else {
-          int r = 0;
-          while (t >= hi - r) { t -= hi - r; r++; }
-          ti = bi * SBK + r;
-          tj = bi * SBK + r + t;
-        }
-        return;
-      }
-      t -= cnt;
-    }
-  }
-  ti = tj = 0;
-}
-
-// Variant 2: LDS-DMA staging (global_load_lds_dwordx4, 1 KiB per wave
+// k_gram_dma: LDS-DMA staging (global_load_lds_dwordx4, 1 KiB per wave
 // instruction written lane-linearly).  The XOR swizzle moves to the per-lane
 // SOURCE address: lane L of an 8-row piece loads chunk (L&7)^((row>>1)&7) of
 // row r0+L/8, so the lane-linear LDS image equals lds_off() layout.
@@ -81,8 +51,7 @@ typedef __attribute__((address_space(3))) void *lptr_t;
 
 __global__ __launch_bounds__(NT, 2) void k_gram_dma(const uint16_t *__restrict__ z, int64_t ld, int nt,
                                                     int ntiles, int64_t nsteps, int sps, int fs,
-                                                    int64_t np_, unsigned long long *__restrict__ gram,
-                                                    int blocked) {
+                                                    int64_t np_, unsigned long long *__restrict__ gram) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE_BYTES];
   const int nwg = gridDim.x;
   const int bid = blockIdx.x;
@@ -91,13 +60,9 @@ __global__ __launch_bounds__(NT, 2) void k_gram_dma(const uint16_t *__restrict__
   const int wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
   const int slice = wid / ntiles;
   int t = wid - slice * ntiles;
-  int ti = 0, tj;
-  if (blocked) {
-    tile_blocked(t, nt, ti, tj);
-  } else {
-    while (t >= nt - ti) { t -= nt - ti; ti++; }
-    tj = ti + t;
-  }
+  int ti = 0;                                    // upper-triangle tile t -> (ti, tj), row-major
+  while (t >= nt - ti) { t -= nt - ti; ti++; }
+  const int tj = ti + t;
   const int64_t s0 = (int64_t)slice * sps;
   int64_t s1 = s0 + sps;
   if (s1 > nsteps) s1 = nsteps;
@@ -128,7 +93,7 @@ __global__ __launch_bounds__(NT, 2) void k_gram_dma(const uint16_t *__restrict__
       for (int r = 0; r < 16; r++) { acc[a][b][r] = 0.0f; iacc[a][b][r] = 0; }
 
 #define GRAM_DMA(step, b)                                                                       \
-  do {                                                                                          \
+  do {                                                                                         \
     char *A_ = smem + (b) * 2 * TILE_BYTES;                                                     \
     char *B_ = A_ + TILE_BYTES;                                                                 \
     const int64_t k_ = (step) * BK;                                                             \
@@ -143,7 +108,7 @@ __global__ __launch_bounds__(NT, 2) void k_gram_dma(const uint16_t *__restrict__
   // one K-step of MFMAs on LDS buffer `b_`; ZERO_ starts a new fp32 chunk by
   // feeding a zero accumulator to the first MFMA (no separate clearing pass)
 #define GRAM_COMPUTE(b_, ZERO_)                                                                \
-  do {                                                                                         \
+  do {                                                                                        \
     const char *A = smem + (b_) * 2 * TILE_BYTES;                                              \
     const char *B = A + TILE_BYTES;                                                            \
     _Pragma("unroll") for (int s = 0; s < 4; s++) {                                            \
@@ -205,225 +170,10 @@ constexpr bool GRAM_WIDE = false;   // default for GRID_GRAM_WIDE (16x16 layout:
 constexpr int SLOT3 = (BM3 + BN3) * BK * 2;     // 48 KiB
 constexpr int QSA = BM3 * BK * 2, QSB = BN3 * BK * 2;   // quad-row image: A / B slot bytes
 
-__device__ __forceinline__ uint4 lds_read_b128(uint32_t addr) {
-  uint4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-
-// Variant 6 (default): 256x128 output tile per 512-thread workgroup (8
-// waves in a 4x2 grid, 64x64 = 2x2 MFMA blocks each, two waves per SIMD), a
-// 3-slot LDS-DMA ring (48 KiB per slot), pipelined so the MFMA pipe stays fed:
-//   * fragments are double-buffered in registers: the ds_reads of sub-step
-//     s+1 are in flight while the MFMAs of sub-step s issue;
-//   * the per-step barrier sits in the middle of the last sub-step, so the
-//     first fragments of the next step are read behind the last MFMAs, and
-//     the slot freed by that barrier immediately receives step st+3 (three
-//     steps of DMA lead);
-//   * the exact fp32 -> int32 flush is staggered: block b restarts its fp32
-//     chunk at sub-step 4b of every 4-step group (chunk = 16 sub-steps =
-//     4 K-steps, exact for qmax <= 256), so a sub-step carries at most one
-//     block's 32 VALU ops between its MFMAs.
-// Work map: 256x128 tiles (I, j >= 2I) in 4x8 super-blocks (one XCD's 32
-// concurrent workgroups share 4 A and 8 B panels in L2).
+// Work map of k_gram8: 256x128 tiles (I, j >= 2I) in 4x8 super-blocks, so the
+// workgroups of one XCD round share 4 A and 8 B panels in its L2
+// (launch_gram8 enumerates the tiles in that order).
 constexpr int GI6 = 4, GJ6 = 8;
-// A wave-uniform pointer forced into SGPRs (keeps global_load_lds in its
-// saddr + 32-bit voffset form instead of 64-bit per-lane addresses).
-__device__ __forceinline__ const char *sgpr_ptr(const char *p) {
-  const uint64_t v = (uint64_t)(uintptr_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return reinterpret_cast<const char *>((uintptr_t)(((uint64_t)hi << 32) | lo));
-}
-__host__ __device__ void tile_blocked6(int t, int nt, int ni, int &I, int &tj) {
-  const int nbI = (ni + GI6 - 1) / GI6;
-  for (int bi = 0; bi < nbI; bi++) {
-    const int i0 = bi * GI6, i1 = min(ni, i0 + GI6);
-    int cnt = 0;
-    for (int i = i0; i < i1; i++) cnt += nt - 2 * i;
-    if (t >= cnt) { t -= cnt; continue; }
-    for (int bj = (2 * i0) / GJ6;; bj++) {
-      const int j0 = bj * GJ6, j1 = min(nt, j0 + GJ6);
-      int c = 0;
-      for (int i = i0; i < i1; i++) c += max(0, j1 - max(j0, 2 * i));
-      if (t >= c) { t -= c; continue; }
-      for (int i = i0; i < i1; i++) {
-        const int lo = max(j0, 2 * i), w = max(0, j1 - lo);
-        if (t < w) { I = i; tj = lo + t; return; }
-        t -= w;
-      }
-    }
-  }
-  I = 0; tj = 0;
-}
-
-#ifdef GRID_PROBES   // k_gram6: tools build only (tools/bench_gram.py A/B and timing probes)
-// One workgroup's pass over K-steps [s0, s1) of output tile (I, tj): fp32
-// MFMA chunks flushed exactly into iacc (which the caller keeps or drains).
-template <int MODE, int SPLIT, int MB, int GS>
-__device__ __forceinline__ void g6_run(const uint16_t *__restrict__ z, int64_t ld, int I, int tj, int64_t s0,
-                                       int64_t s1, char *smem, f32x16 (&acc)[MB][2],
-                                       int32_t (&iacc)[MB][2][16]) {
-  constexpr int NW = MB == 2 ? 8 : 4;           // waves
-  constexpr int RA = BM3 / NW, RB = BN3 / NW;   // DMA rows per wave (A, B)
-  constexpr int UA = RA / 8, UB = RB / 8;       // 1-KiB DMA pieces per wave (A, B)
-  constexpr int NDMA = UA + UB;                 // DMA instructions per wave per K-step
-  constexpr int NF = MB + 2;                    // fragments per sub-step
-  constexpr int FSP = 4 * GS / (2 * MB);        // sub-steps between block flushes
-  constexpr bool NOLOAD = MODE == 5 || MODE == 6, NOFLUSH = MODE == 2 || MODE == 6;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int rl = lane >> 3, cx = lane & 7;
-  // Addresses: wave-uniform 64-bit row-piece bases (SGPRs, saddr form) plus a
-  // 32-bit per-lane byte offset (row rl of the piece, swizzled chunk).
-  const int wv = __builtin_amdgcn_readfirstlane(wave);
-  const int sa = ((wv * RA + rl) >> 1) & 7, sb = ((wv * RB + rl) >> 1) & 7;
-  const uint32_t voa0 = (uint32_t)((rl * ld + ((cx ^ sa) * 8)) * 2);
-  const uint32_t voa1 = (uint32_t)((rl * ld + ((cx ^ sa ^ 4) * 8)) * 2);
-  const uint32_t vob0 = (uint32_t)((rl * ld + ((cx ^ sb) * 8)) * 2);
-  const uint32_t vob1 = (uint32_t)((rl * ld + ((cx ^ sb ^ 4) * 8)) * 2);
-  const char *ga = reinterpret_cast<const char *>(z + ((int64_t)I * BM3 + wv * RA) * ld);
-  const char *gb = reinterpret_cast<const char *>(z + ((int64_t)tj * BN3 + wv * RB) * ld);
-  const int64_t ld8b = 16 * ld;       // bytes per 8 rows
-  const uint32_t sbase = (uint32_t)(uintptr_t)smem;
-  // fragment byte offsets inside a slot at sub-step 0 (chunk lane/32); sub-step
-  // s reads chunk 2s + lane/32, i.e. the offset XOR (s << 5)
-  uint32_t offa[MB], offb[2];
-#pragma unroll
-  for (int m = 0; m < MB; m++) offa[m] = lds_off(wr * (32 * MB) + m * 32 + (lane & 31), lane >> 5);
-#pragma unroll
-  for (int nn = 0; nn < 2; nn++) offb[nn] = BM3 * 128 + lds_off(wc * 64 + nn * 32 + (lane & 31), lane >> 5);
-
-  const f32x16 zero16 = {};
-  uint4 fr0[NF], fr1[NF];
-
-#define G6_WAIT_VM(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
-#define G6_WAIT_LGKM(n_) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n_) : "memory")
-#define G6_ISSUE(step_, slot_)                                                                 \
-  if (!NOLOAD) do {                                                                           \
-    char *A_ = smem + (slot_) * SLOT3;                                                         \
-    const int64_t kb_ = (step_) * (BK * 2);                                                    \
-    _Pragma("unroll") for (int u = 0; u < UA; u++)                                             \
-      __builtin_amdgcn_global_load_lds((gptr_t)(sgpr_ptr(ga + (u * ld8b + kb_)) + ((u & 1) ? voa1 : voa0)), \
-                                       (lptr_t)(A_ + (wv * RA + u * 8) * 128), 16, 0, 0);      \
-    _Pragma("unroll") for (int u = 0; u < UB; u++)                                             \
-      __builtin_amdgcn_global_load_lds((gptr_t)(sgpr_ptr(gb + (u * ld8b + kb_)) + ((u & 1) ? vob1 : vob0)), \
-                                       (lptr_t)(A_ + BM3 * 128 + (wv * RB + u * 8) * 128), 16, 0, 0); \
-  } while (0)
-#define G6_READ(FR, base_, s_)                                                                 \
-  do {                                                                                         \
-    if (MODE != 4) _Pragma("unroll") for (int m = 0; m < MB; m++) FR[m] = lds_read_b128((base_) + (offa[m] ^ ((s_) << 5))); \
-    _Pragma("unroll") for (int nn = 0; nn < 2; nn++) FR[MB + nn] = lds_read_b128((base_) + (offb[nn] ^ ((s_) << 5))); \
-  } while (0)
-  // MFMAs of blocks m in [m0, m1) on fragments FR at in-group sub-step c_;
-  // block b = 2m + nn restarts its fp32 chunk at sub-step FSP*b
-#define G6_MFMA(FR, c_, m0, m1, STAG)                                                          \
-  do {                                                                                         \
-    _Pragma("unroll") for (int m = m0; m < m1; m++)                                            \
-      _Pragma("unroll") for (int nn = 0; nn < 2; nn++) {                                       \
-        if ((STAG) && (c_) == FSP * (m * 2 + nn)) {                                            \
-          _Pragma("unroll") for (int r = 0; r < 16; r++) iacc[m][nn][r] += (int32_t)acc[m][nn][r]; \
-          acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(FR[m]), as_bf16x8(FR[MB + nn]), \
-                                                               zero16, 0, 0, 0);               \
-        } else {                                                                               \
-          acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(FR[m]), as_bf16x8(FR[MB + nn]), \
-                                                               acc[m][nn], 0, 0, 0);           \
-        }                                                                                      \
-      }                                                                                        \
-  } while (0)
-  // one K-step `st_` (LDS slot `slot`), in-group index q_; fr0 holds sub-step 0 on entry
-#define G6_STEP(st_, q_, STAG, COND)                                                           \
-  do {                                                                                         \
-    const uint32_t base_ = sbase + slot * SLOT3;                                               \
-    G6_READ(fr1, base_, 1);                                                                    \
-    G6_WAIT_LGKM(MODE == 4 ? 2 : NF);                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_MFMA(fr0, 4 * (q_) + 0, 0, MB, STAG);                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_READ(fr0, base_, 2);                                                                    \
-    G6_WAIT_LGKM(MODE == 4 ? 2 : NF);                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_MFMA(fr1, 4 * (q_) + 1, 0, MB, STAG);                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_READ(fr1, base_, 3);                                                                    \
-    G6_WAIT_LGKM(MODE == 4 ? 2 : NF);                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_MFMA(fr0, 4 * (q_) + 2, 0, MB, STAG);                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_WAIT_LGKM(0);                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_MFMA(fr1, 4 * (q_) + 3, 0, SPLIT, STAG);                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    if (!(COND) || (st_) + 2 < s1) G6_WAIT_VM(NDMA);                                           \
-    else G6_WAIT_VM(0);                                                                        \
-    __builtin_amdgcn_s_barrier();                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    if (!(COND) || (st_) + 3 < s1) G6_ISSUE((st_) + 3, slot);                                  \
-    slot = slot == 2 ? 0 : slot + 1;                                                           \
-    if (!(COND) || (st_) + 1 < s1) G6_READ(fr0, sbase + slot * SLOT3, 0);                      \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-    G6_MFMA(fr1, 4 * (q_) + 3, SPLIT, MB, STAG);                                               \
-    __builtin_amdgcn_sched_barrier(0);                                                         \
-  } while (0)
-#define G6_FLUSH()                                                                             \
-  do {                                                                                         \
-    _Pragma("unroll") for (int a = 0; a < MB; a++)                                             \
-      _Pragma("unroll") for (int b = 0; b < 2; b++)                                            \
-        _Pragma("unroll") for (int r = 0; r < 16; r++) {                                       \
-          iacc[a][b][r] += (int32_t)acc[a][b][r];                                              \
-          acc[a][b][r] = 0.0f;                                                                 \
-        }                                                                                      \
-  } while (0)
-
-  int slot = 0;
-  if (s0 < s1) {
-    G6_ISSUE(s0, 0);
-    if (s0 + 1 < s1) G6_ISSUE(s0 + 1, 1);
-    if (s0 + 2 < s1) G6_ISSUE(s0 + 2, 2);
-    if (s0 + 2 < s1) G6_WAIT_VM(2 * NDMA);
-    else if (s0 + 1 < s1) G6_WAIT_VM(NDMA);
-    else G6_WAIT_VM(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    G6_READ(fr0, sbase, 0);
-  }
-  int64_t st = s0;
-  const int64_t sfull = s0 + ((s1 - s0) / GS) * GS;
-  // steady state: every step's DMA lead (st+3) exists
-  for (; st < sfull && st + GS + 2 < s1; st += GS) {
-    G6_STEP(st, 0, !NOFLUSH, 0);
-    G6_STEP(st + 1, 1, !NOFLUSH, 0);
-    G6_STEP(st + 2, 2, !NOFLUSH, 0);
-    G6_STEP(st + 3, 3, !NOFLUSH, 0);
-    if constexpr (GS == 6) {
-      G6_STEP(st + 4, 4, !NOFLUSH, 0);
-      G6_STEP(st + 5, 5, !NOFLUSH, 0);
-    }
-  }
-  for (; st < sfull; st += GS) {
-    G6_STEP(st, 0, !NOFLUSH, 1);
-    G6_STEP(st + 1, 1, !NOFLUSH, 1);
-    G6_STEP(st + 2, 2, !NOFLUSH, 1);
-    G6_STEP(st + 3, 3, !NOFLUSH, 1);
-    if constexpr (GS == 6) {
-      G6_STEP(st + 4, 4, !NOFLUSH, 1);
-      G6_STEP(st + 5, 5, !NOFLUSH, 1);
-    }
-  }
-  G6_FLUSH();
-  for (; st < s1; st++) G6_STEP(st, 0, 0, 1);
-  G6_FLUSH();
-#undef G6_WAIT_VM
-#undef G6_WAIT_LGKM
-#undef G6_ISSUE
-#undef G6_READ
-#undef G6_MFMA
-#undef G6_STEP
-#undef G6_FLUSH
-}
-
-#endif  // GRID_PROBES
 
 // Drain iacc into the int64 Gram (order-free integer atomics) and clear it.
 template <int MB>
@@ -510,40 +260,6 @@ __device__ __forceinline__ void g6_zero(f32x16 (&acc)[MB][2], int32_t (&iacc)[MB
       for (int r = 0; r < 16; r++) { acc[a][b][r] = 0.0f; iacc[a][b][r] = 0; }
 }
 
-#ifdef GRID_PROBES
-// MODE 0: production.  Timing probes (wrong results, tools/bench_gram.py):
-// 1 every tile reads the same panels (all L2 hits); 2 = 1 without the flush;
-// 4 = 1 with half the fragment reads; 5 = 1 without any global loads;
-// 3 = production without the XCD remap.  MB = 32-row A blocks per wave:
-// 2 -> 8 waves (4x2 grid, 64x64 each, two waves per SIMD); 4 -> 4 waves
-// (128x64 each; needs more than the 512 registers hipcc will give it).
-template <int MODE, int SPLIT, int MB, int GS>
-__global__ __launch_bounds__(MB == 2 ? 512 : 256, 1) void k_gram6(const uint16_t *__restrict__ z, int64_t ld,
-                                                                  int nt, int ni, int ntiles, int64_t nsteps,
-                                                                  int sps, int64_t np_,
-                                                                  unsigned long long *__restrict__ gram) {
-  __shared__ __attribute__((aligned(16))) char smem[3 * SLOT3];
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, loc = bid >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wid = MODE == 3 ? bid : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-  const int slice = wid / ntiles;
-  int I = 0, tj = 0;
-  tile_blocked6(wid - slice * ntiles, nt, ni, I, tj);
-  if (MODE == 1 || MODE == 2 || MODE == 4 || MODE == 5 || MODE == 6) { I = 0; tj = 0; }
-  const int64_t s0 = (int64_t)slice * sps;
-  int64_t s1 = s0 + sps;
-  if (s1 > nsteps) s1 = nsteps;
-  f32x16 acc[MB][2];
-  int32_t iacc[MB][2][16];
-  g6_zero<MB>(acc, iacc);
-  g6_run<MODE, SPLIT, MB, GS>(z, ld, I, tj, s0, s1, smem, acc, iacc);
-  g6_atomics<MB>(iacc, I, tj, np_, gram);
-}
-
-#endif  // GRID_PROBES
-
 // Default Gram kernel (k_gram8): persistent, one 512-thread workgroup per CU,
 // XCD x = blockIdx % 8 (placement is a performance assumption only; results
 // never depend on it).  XCD x owns K-steps [x*S/8, (x+1)*S/8) split into kc
@@ -556,28 +272,20 @@ __global__ __launch_bounds__(MB == 2 ? 512 : 256, 1) void k_gram6(const uint16_t
 //
 // The K loop does no address arithmetic and fits 256 registers without
 // spills (a spill reload's vmcnt(0) would drain the LDS-DMA ring):
-//   * LDS slot (48 KiB): A rows 0..255 then B rows 0..127, in 8-row blocks of
-//     1 KiB laid out [sub-step s (4)][row r (8)][32 B]; the 32 B of (row, s)
-//     hold the K chunks 2s, 2s+1 in the order h ^ (block & 1).  The fragment
-//     of sub-step s is at base + 256 s: one VGPR per (slot, fragment) plus an
-//     immediate offset.  The 16 lanes of a ds_read_b128 quarter hit 16
-//     distinct 16-B bank groups (rows of an even block on h, odd on h ^ 1).
-//   * DMA: buffer_load_dwordx4 ... lds; lane l of an 8-row block loads row
-//     (l >> 1) & 7, chunk 2 (l >> 4) + ((l & 1) ^ (block & 1)), so each
-//     instruction still reads 8 whole 128-B row segments.  Panel base in the
-//     descriptor (SGPRs), row offsets in 4 VGPRs, the K offset in soffset.
-//   * BL: the panel is K-blocked, [K-step][row][64] (the layout zquant writes
-//     for the fused chain): a K-step of a 256-row panel is one contiguous
-//     32 KiB run instead of 256 rows 2*ld bytes apart (-9 % time: fewer pages
+//   * LDS: a ring of 3 slots of 48 KiB (a K-step of 256 A and 128 B rows); one
+//     VGPR per fragment base, the slot and sub-step as immediate offsets.  The
+//     images (conflict-free for ds_read_b128) are described at g8_run (quad-row,
+//     row-major panel), g8h_run and g8q_run (half-split, K-blocked panel).
+//   * DMA: buffer_load_dwordx4 ... lds in whole 64-B row pieces.  Panel base in
+//     the descriptor (SGPRs), row offsets in VGPRs, the K offset in soffset.
+//   * BL: the panel is K-blocked, [kpad / 32][row][32] (the layout zquant writes
+//     for the fused chain): a K-half of a 256-row panel is one contiguous
+//     16 KiB run instead of 256 rows 2*ld bytes apart (-9 % time: fewer pages
 //     and DRAM rows per step).
 //   * fp32 chunks: a 6-step group (24 sub-steps) walks the 3 ring slots twice,
 //     so slots are compile-time; block b = 2m + nn restarts its fp32 chunk at
 //     sub-steps 6b (FL = 1: 384-product chunks, exact while 384 qmax^2 <= 2^24,
 //     qmax <= 209) or 3b and 12 + 3b (FL = 2: 192 products, qmax <= 256).
-// MODE 0 production; timing probes (wrong results, tools/bench_gram.py):
-// 1 = every tile reads panel 0 (L2-resident loads), 5 = no global loads,
-// 6 = no global loads and no flush, 7 = no MFMAs (DMA + LDS reads + barriers),
-// 8 = DMA + barriers only (no LDS reads, no MFMAs).
 template <int OFF>
 __device__ __forceinline__ uint4 lds_rd(uint32_t addr) {
   uint4 v;
@@ -585,69 +293,51 @@ __device__ __forceinline__ uint4 lds_rd(uint32_t addr) {
   return v;
 }
 
-// QL (quad-row image, the default): a lane quad of every LDS-DMA piece reads 64
+// Row-major panel, quad-row image: a lane quad of every LDS-DMA piece reads 64
 // contiguous bytes of ONE panel row (the texture path then moves a piece at
-// twice the rate of the pair-row pieces above: 146 vs 75 GB/s per CU from L2,
-// tools/micro/dmapat.hip).  Piece (8-row block b) = [half p (2)][row r (8)][64 B],
+// twice the rate of pieces whose lane pairs read 32 B: 146 vs 75 GB/s per CU
+// from L2, tools/micro/dmapat.hip).  Piece (8-row block b) = [half p (2)][row r (8)][64 B],
 // the 16-B chunk j of a half stored at j ^ (b & 3); A slots at 0/32/64 KiB,
 // B slots at 96/112/128 KiB.  Fragment of sub-step s = chunk 2s + h of row R:
 // base(s & 1) + 512 (s >> 1) (+ slot offset), where the odd base is the even one
 // ^ 32; each ds_read_b128 lane group sees 4 rows x 4 distinct x = b & 3, i.e.
 // 16 distinct 16-B bank slots (conflict-free).
-template <int MODE, bool BL, int FL, bool QL>
+template <int FL>
 __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t ld, int I, int tj, int64_t s0,
                                        int64_t s1, char *smem, f32x16 (&acc)[2][2],
                                        int32_t (&iacc)[2][2][16]) {
   constexpr int NF = 4, NDMA = 6;
   constexpr int FCYC = 24 / FL, FSP = FCYC / 4;   // flush cycle and stagger, in sub-steps
-  constexpr bool NOLOAD = MODE == 5 || MODE == 6, NOFLUSH = MODE == 6;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int wr = wv >> 1, wc = wv & 1;
-  // DMA sources: this wave's 32 A rows and 16 B rows.  Row-major: base in the
-  // descriptor, K offset in soffset.  BL: per-step descriptor base (a K-block
-  // stride of ld elements exceeds 32-bit offsets).
-  const int64_t rs_el = BL ? BK : ld;                                          // row stride (elements)
+  // DMA sources: this wave's 32 A rows and 16 B rows; base in the descriptor,
+  // K offset in soffset.
+  const int64_t rs_el = ld;                                                    // row stride (elements)
   const uint16_t *pa0 = z + ((int64_t)I * BM3 + wv * 32) * rs_el;
   const uint16_t *pb0 = z + ((int64_t)tj * BN3 + wv * 16) * rs_el;
-  const __amdgpu_buffer_rsrc_t rsa0 = __builtin_amdgcn_make_buffer_rsrc((void *)pa0, (short)0, -1, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsb0 = __builtin_amdgcn_make_buffer_rsrc((void *)pb0, (short)0, -1, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void *)pa0, (short)0, -1, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void *)pb0, (short)0, -1, 0x00020000);
   const uint32_t rb8 = (uint32_t)(16 * rs_el);                                 // bytes per 8 rows
-  uint32_t vo0, vo1, vo2, vo3, vb0, vb1;
-  if constexpr (QL) {
-    const int qr = (lane >> 2) & 7, qp = lane >> 5, qj = lane & 3;
-    auto vq = [&](int x) { return (uint32_t)((qr * rs_el + (4 * qp + (qj ^ x)) * 8) * 2); };
-    vo0 = vq(0); vo1 = vq(1) + rb8; vo2 = vq(2) + 2 * rb8; vo3 = vq(3) + 3 * rb8;
-    const int xb = 2 * (wv & 1);                                               // B blocks 2 wv + t
-    vb0 = vq(xb); vb1 = vq(xb + 1) + rb8;
-  } else {
-    const int dr = (lane >> 1) & 7, ds = lane >> 4, dj = lane & 1;
-    const uint32_t v0 = (uint32_t)((dr * rs_el + (2 * ds + dj) * 8) * 2);        // even block
-    const uint32_t v1 = (uint32_t)((dr * rs_el + (2 * ds + (dj ^ 1)) * 8) * 2);  // odd block
-    vo0 = v0; vo1 = v1 + rb8; vo2 = v0 + 2 * rb8; vo3 = v1 + 3 * rb8;
-    vb0 = vo0; vb1 = vo1;
-  }
+  const int qr = (lane >> 2) & 7, qp = lane >> 5, qj = lane & 3;
+  auto vq = [&](int x) { return (uint32_t)((qr * rs_el + (4 * qp + (qj ^ x)) * 8) * 2); };
+  const uint32_t vo0 = vq(0), vo1 = vq(1) + rb8, vo2 = vq(2) + 2 * rb8, vo3 = vq(3) + 3 * rb8;
+  const int xb = 2 * (wv & 1);                                                 // B blocks 2 wv + t
+  const uint32_t vb0 = vq(xb), vb1 = vq(xb + 1) + rb8;
   const uint32_t sbase = (uint32_t)(uintptr_t)smem;
-  // fragment bases per (slot, fragment): A blocks m = 0, 1; B blocks nn = 0, 1
-  // (QL: per (parity of s, fragment), slot 2 of A separately: offsets < 64 KiB)
+  // fragment bases per (parity of s, fragment): A blocks m = 0, 1; B blocks
+  // nn = 0, 1; slot 2 of A separately (offsets stay < 64 KiB)
   uint32_t ad[3][4];
 #pragma unroll
   for (int f = 0; f < 4; f++) {
     const int R = f < 2 ? wr * 64 + f * 32 + (lane & 31) : wc * 64 + (f - 2) * 32 + (lane & 31);
     const int rb = R >> 3;
-    if constexpr (QL) {
-      const uint32_t ev = sbase + (f < 2 ? 0 : 3 * QSA) + rb * 1024 + (R & 7) * 64 + (((lane >> 5) ^ (rb & 3)) << 4);
-      ad[0][f] = ev;
-      ad[1][f] = ev ^ 32u;
-      if (f < 2) {                      // A, slot 2: [2][m] even, [2][2 + m] odd
-        ad[2][f] = ev + 2 * QSA;
-        ad[2][f + 2] = (ev ^ 32u) + 2 * QSA;
-      }
-    } else {
-#pragma unroll
-      for (int sl = 0; sl < 3; sl++)
-        ad[sl][f] = sbase + sl * SLOT3 + (f < 2 ? 0 : BM3 * 128) + rb * 1024 + (R & 7) * 32 +
-                    (((lane >> 5) ^ (rb & 1)) << 4);
+    const uint32_t ev = sbase + (f < 2 ? 0 : 3 * QSA) + rb * 1024 + (R & 7) * 64 + (((lane >> 5) ^ (rb & 3)) << 4);
+    ad[0][f] = ev;
+    ad[1][f] = ev ^ 32u;
+    if (f < 2) {                        // A, slot 2: [2][m] even, [2][2 + m] odd
+      ad[2][f] = ev + 2 * QSA;
+      ad[2][f + 2] = (ev ^ 32u) + 2 * QSA;
     }
   }
   const f32x16 zero16 = {};
@@ -657,14 +347,10 @@ __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t l
 #define G8_WAIT_LGKM(n_) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n_) : "memory")
 #define G8_SB() __builtin_amdgcn_sched_barrier(0)
 #define G8_ISSUE(step_, SL)                                                                    \
-  if (!NOLOAD) do {                                                                            \
-    const uint32_t so_ = BL ? 0u : (uint32_t)((step_) * (BK * 2));                             \
-    const __amdgpu_buffer_rsrc_t rsa = BL ? __builtin_amdgcn_make_buffer_rsrc(                 \
-        (void *)(pa0 + (int64_t)(step_) * ld), (short)0, -1, 0x00020000) : rsa0;               \
-    const __amdgpu_buffer_rsrc_t rsb = BL ? __builtin_amdgcn_make_buffer_rsrc(                 \
-        (void *)(pb0 + (int64_t)(step_) * ld), (short)0, -1, 0x00020000) : rsb0;               \
-    char *A_ = smem + (SL) * (QL ? QSA : SLOT3) + wv * 4096;                                   \
-    char *B_ = smem + (QL ? 3 * QSA + (SL) * QSB : (SL) * SLOT3 + BM3 * 128) + wv * 2048;      \
+  do {                                                                                         \
+    const uint32_t so_ = (uint32_t)((step_) * (BK * 2));                                       \
+    char *A_ = smem + (SL) * QSA + wv * 4096;                                                  \
+    char *B_ = smem + 3 * QSA + (SL) * QSB + wv * 2048;                                        \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_), 16, vo0, so_, 0, 0);           \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_ + 1024), 16, vo1, so_, 0, 0);    \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_ + 2048), 16, vo2, so_, 0, 0);    \
@@ -673,26 +359,19 @@ __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t l
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lptr_t)(B_ + 1024), 16, vb1, so_, 0, 0);    \
   } while (0)
 #define G8_READ(FR, SL, s_)                                                                    \
-  if (MODE != 8) do {                                                                          \
-    if constexpr (QL) {                                                                        \
-      constexpr int pa_ = (s_) & 1, ia_ = (SL) == 2 ? 2 : pa_, ja_ = (SL) == 2 ? 2 * pa_ : 0;  \
-      constexpr int oa_ = ((SL) == 2 ? 0 : (SL) * QSA) + ((s_) >> 1) * 512;                    \
-      constexpr int ob_ = (SL) * QSB + ((s_) >> 1) * 512;                                      \
-      FR[0] = lds_rd<oa_>(ad[ia_][ja_]);                                                       \
-      FR[1] = lds_rd<oa_>(ad[ia_][ja_ + 1]);                                                   \
-      FR[2] = lds_rd<ob_>(ad[pa_][2]);                                                         \
-      FR[3] = lds_rd<ob_>(ad[pa_][3]);                                                         \
-    } else {                                                                                   \
-      FR[0] = lds_rd<(s_) * 256>(ad[SL][0]);                                                   \
-      FR[1] = lds_rd<(s_) * 256>(ad[SL][1]);                                                   \
-      FR[2] = lds_rd<(s_) * 256>(ad[SL][2]);                                                   \
-      FR[3] = lds_rd<(s_) * 256>(ad[SL][3]);                                                   \
-    }                                                                                          \
+  do {                                                                                         \
+    constexpr int pa_ = (s_) & 1, ia_ = (SL) == 2 ? 2 : pa_, ja_ = (SL) == 2 ? 2 * pa_ : 0;    \
+    constexpr int oa_ = ((SL) == 2 ? 0 : (SL) * QSA) + ((s_) >> 1) * 512;                      \
+    constexpr int ob_ = (SL) * QSB + ((s_) >> 1) * 512;                                        \
+    FR[0] = lds_rd<oa_>(ad[ia_][ja_]);                                                         \
+    FR[1] = lds_rd<oa_>(ad[ia_][ja_ + 1]);                                                     \
+    FR[2] = lds_rd<ob_>(ad[pa_][2]);                                                           \
+    FR[3] = lds_rd<ob_>(ad[pa_][3]);                                                           \
   } while (0)
   // MFMAs of A blocks [m0, m1) at in-group sub-step c_; block b = 2m + nn starts
   // a new fp32 chunk (after flushing the old one) at sub-steps = FSP b (mod FCYC)
 #define G8_MFMA(FR, c_, m0, m1, STAG)                                                          \
-  if (MODE != 7 && MODE != 8) do {                                                             \
+  do {                                                                                         \
     _Pragma("unroll") for (int m = m0; m < m1; m++)                                            \
       _Pragma("unroll") for (int nn = 0; nn < 2; nn++) {                                       \
         if ((STAG) && ((c_) % FCYC) == FSP * (m * 2 + nn)) {                                   \
@@ -709,7 +388,7 @@ __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t l
   // its sub-step 0 on entry and the next step's sub-step 0 on exit.  The
   // barrier sits inside the last sub-step; the slot it frees receives st_ + 3.
 #define G8_STEP(st_, q_, SL, STAG, COND)                                                       \
-  do {                                                                                         \
+  do {                                                                                        \
     G8_READ(fr1, SL, 1);                                                                       \
     G8_WAIT_LGKM(NF); G8_SB();                                                                 \
     G8_MFMA(fr0, 4 * (q_) + 0, 0, 2, STAG); G8_SB();                                           \
@@ -730,7 +409,7 @@ __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t l
     G8_MFMA(fr1, 4 * (q_) + 3, 1, 2, STAG); G8_SB();                                           \
   } while (0)
 #define G8_FLUSH()                                                                             \
-  do {                                                                                         \
+  do {                                                                                        \
     _Pragma("unroll") for (int a = 0; a < 2; a++)                                              \
       _Pragma("unroll") for (int b = 0; b < 2; b++)                                            \
         _Pragma("unroll") for (int r = 0; r < 16; r++) {                                       \
@@ -753,20 +432,20 @@ __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t l
   const int64_t sfull = s0 + ((s1 - s0) / 6) * 6;
   // steady state: every step's DMA lead (st + 3) exists
   for (; st < sfull && st + 8 < s1; st += 6) {
-    G8_STEP(st, 0, 0, !NOFLUSH, 0);
-    G8_STEP(st + 1, 1, 1, !NOFLUSH, 0);
-    G8_STEP(st + 2, 2, 2, !NOFLUSH, 0);
-    G8_STEP(st + 3, 3, 0, !NOFLUSH, 0);
-    G8_STEP(st + 4, 4, 1, !NOFLUSH, 0);
-    G8_STEP(st + 5, 5, 2, !NOFLUSH, 0);
+    G8_STEP(st, 0, 0, 1, 0);
+    G8_STEP(st + 1, 1, 1, 1, 0);
+    G8_STEP(st + 2, 2, 2, 1, 0);
+    G8_STEP(st + 3, 3, 0, 1, 0);
+    G8_STEP(st + 4, 4, 1, 1, 0);
+    G8_STEP(st + 5, 5, 2, 1, 0);
   }
   for (; st < sfull; st += 6) {
-    G8_STEP(st, 0, 0, !NOFLUSH, 1);
-    G8_STEP(st + 1, 1, 1, !NOFLUSH, 1);
-    G8_STEP(st + 2, 2, 2, !NOFLUSH, 1);
-    G8_STEP(st + 3, 3, 0, !NOFLUSH, 1);
-    G8_STEP(st + 4, 4, 1, !NOFLUSH, 1);
-    G8_STEP(st + 5, 5, 2, !NOFLUSH, 1);
+    G8_STEP(st, 0, 0, 1, 1);
+    G8_STEP(st + 1, 1, 1, 1, 1);
+    G8_STEP(st + 2, 2, 2, 1, 1);
+    G8_STEP(st + 3, 3, 0, 1, 1);
+    G8_STEP(st + 4, 4, 1, 1, 1);
+    G8_STEP(st + 5, 5, 2, 1, 1);
   }
   G8_FLUSH();
   // tail (< 6 steps): slot (st - s0) % 3 known at run time; one fp32 chunk
@@ -789,37 +468,34 @@ __device__ __forceinline__ void g8_run(const uint16_t *__restrict__ z, int64_t l
 #undef G8_FLUSH
 }
 
-// LAY 2 (half-split image): every ring slot holds a K-step as two halves
-// (K chunks 0-3 | 4-7, 64 B of each panel row), region [half p][row][64 B]
+// LAY 3 (K-blocked panel, half-split image): every ring slot holds a K-step as
+// two halves (K chunks 0-3 | 4-7, 64 B of each panel row), region [half p][row][64 B]
 // with the 16-B chunk j of row R stored at j ^ ((R >> 2) & 3).  A DMA piece is
 // 16 rows x 64 B (lane quad = 64 contiguous bytes of one row; ONE voffset VGPR,
-// the piece's rows and half in soffset).  Sub-steps 0-1 read half 0 and 2-3
+// the piece's rows in soffset, its K-half in the descriptor base: a K-block
+// stride of ld / 2 elements exceeds 32-bit offsets).  Sub-steps 0-1 read half 0 and 2-3
 // half 1, so each half of slot st is refilled with step st + 3 as soon as
 // every wave has read it: two barriers per step, each followed by 3 pieces
 // per wave (the texture path's work spread over the step instead of one
 // 6-piece burst behind a single barrier), and 2.5 steps of DMA lead.
 // Fragment bases: even / odd sub-steps (odd = even ^ 32), half offsets and
 // slots as immediates (A slot 2 has its own bases: offsets stay < 64 KiB).
-// K32 (tools A/B, LAY 3): the panel K-blocked by 32 columns, [K-half][row][32],
-// so a 16-row half piece is 1 KiB contiguous (whole 128-B lines; with the
-// 64-wide blocks a half piece reads half of every line it touches).
-template <int MODE, bool BL, int FL, bool K32 = false>
+// The panel is K-blocked by 32 columns, [K-half][row][32], so a 16-row half
+// piece is 1 KiB contiguous (whole 128-B lines).
+// FL = 1 is kept only for the GRID_ISA_PROBE pair (tools/isa_barriers.py --probe); the product runs FL = 2 here.
+template <int FL>
 __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t ld, int I, int tj, int64_t s0,
                                         int64_t s1, char *smem, f32x16 (&acc)[2][2],
                                         int32_t (&iacc)[2][2][16]) {
   constexpr int NF = 4;
   constexpr int FCYC = 24 / FL, FSP = FCYC / 4;
   constexpr int HA = QSA / 2, HB = QSB / 2;             // half regions of a slot (A, B)
-  constexpr bool NOLOAD = MODE == 5 || MODE == 6, NOFLUSH = MODE == 6;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int wr = wv >> 1, wc = wv & 1;
-  static_assert(!K32 || BL, "K32 is a K-blocked layout");
-  const int64_t rs_el = K32 ? BK / 2 : BL ? BK : ld;
+  constexpr int64_t rs_el = BK / 2;                     // 64-B rows
   const uint16_t *pa0 = z + ((int64_t)I * BM3 + wv * 32) * rs_el;
   const uint16_t *pb0 = z + ((int64_t)tj * BN3 + wv * 16) * rs_el;
-  const __amdgpu_buffer_rsrc_t rsa0 = __builtin_amdgcn_make_buffer_rsrc((void *)pa0, (short)0, -1, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsb0 = __builtin_amdgcn_make_buffer_rsrc((void *)pb0, (short)0, -1, 0x00020000);
   const uint32_t vq = (uint32_t)(((lane >> 2) * rs_el + ((lane & 3) ^ ((lane >> 4) & 3)) * 8) * 2);
   const uint32_t r16 = (uint32_t)(32 * rs_el);         // bytes per 16 rows
   const uint32_t sbase = (uint32_t)(uintptr_t)smem;
@@ -843,21 +519,20 @@ __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t 
 #define H8_SB() __builtin_amdgcn_sched_barrier(0)
   // half P of K-step step_ into ring slot SL: A rows wv*32 + {0..15, 16..31}, B rows wv*16 + 0..15
 #define H8_ISSUE(step_, P, SL)                                                                 \
-  if (!NOLOAD) do {                                                                            \
-    const uint32_t so_ = K32 ? 0u : (BL ? 0u : (uint32_t)((step_) * (BK * 2))) + (P) * 64u;    \
-    const int64_t ko_ = K32 ? (2 * (int64_t)(step_) + (P)) * (ld >> 1) : (int64_t)(step_) * ld; \
-    const __amdgpu_buffer_rsrc_t rsa = BL ? __builtin_amdgcn_make_buffer_rsrc(                 \
-        (void *)(pa0 + ko_), (short)0, -1, 0x00020000) : rsa0;                                 \
-    const __amdgpu_buffer_rsrc_t rsb = BL ? __builtin_amdgcn_make_buffer_rsrc(                 \
-        (void *)(pb0 + ko_), (short)0, -1, 0x00020000) : rsb0;                                 \
+  do {                                                                                         \
+    const int64_t ko_ = (2 * (int64_t)(step_) + (P)) * (ld >> 1);                              \
+    const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(                      \
+        (void *)(pa0 + ko_), (short)0, -1, 0x00020000);                                        \
+    const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(                      \
+        (void *)(pb0 + ko_), (short)0, -1, 0x00020000);                                        \
     char *A_ = smem + (SL) * QSA + (P) * HA + wv * 2048;                                       \
     char *B_ = smem + 3 * QSA + (SL) * QSB + (P) * HB + wv * 1024;                             \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_), 16, vq, so_, 0, 0);            \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_ + 1024), 16, vq, so_ + r16, 0, 0); \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lptr_t)(B_), 16, vq, so_, 0, 0);            \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_), 16, vq, 0, 0, 0);              \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lptr_t)(A_ + 1024), 16, vq, r16, 0, 0);     \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lptr_t)(B_), 16, vq, 0, 0, 0);              \
   } while (0)
 #define H8_READ(FR, SL, s_)                                                                    \
-  if (MODE != 8) do {                                                                          \
+  do {                                                                                         \
     constexpr int pa_ = (s_) & 1, ia_ = (SL) == 2 ? 2 : pa_, ja_ = (SL) == 2 ? 2 * pa_ : 0;    \
     constexpr int oa_ = ((SL) == 2 ? 0 : (SL) * QSA) + ((s_) >> 1) * HA;                       \
     constexpr int ob_ = (SL) * QSB + ((s_) >> 1) * HB;                                         \
@@ -867,7 +542,7 @@ __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t 
     FR[3] = lds_rd<ob_>(ad[pa_][3]);                                                           \
   } while (0)
 #define H8_MFMA(FR, c_, m0, m1, STAG)                                                          \
-  if (MODE != 7 && MODE != 8) do {                                                             \
+  do {                                                                                         \
     _Pragma("unroll") for (int m = m0; m < m1; m++)                                            \
       _Pragma("unroll") for (int nn = 0; nn < 2; nn++) {                                       \
         if ((STAG) && ((c_) % FCYC) == FSP * (m * 2 + nn)) {                                   \
@@ -883,14 +558,14 @@ __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t 
   // vmcnt before barrier 1 of step st: the wave's pieces of (st, half 1) have
   // landed; younger: (st+1, *), (st+2, *) -- 3 pieces per half
 #define H8_VM1(st_, COND)                                                                      \
-  do {                                                                                         \
+  do {                                                                                        \
     if (!(COND) || (st_) + 2 < s1) H8_WAIT_VM(12);                                             \
     else if ((st_) + 1 < s1) H8_WAIT_VM(6);                                                    \
     else H8_WAIT_VM(0);                                                                        \
   } while (0)
   // before barrier 2: (st+1, half 0) landed; younger: (st+1, 1), (st+2, *), (st+3, 0)
 #define H8_VM2(st_, COND)                                                                      \
-  do {                                                                                         \
+  do {                                                                                        \
     if (!(COND) || (st_) + 3 < s1) H8_WAIT_VM(12);                                             \
     else if ((st_) + 2 < s1) H8_WAIT_VM(9);                                                    \
     else if ((st_) + 1 < s1) H8_WAIT_VM(3);                                                    \
@@ -899,7 +574,7 @@ __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t 
   // K-step st_ in ring slot SL (compile-time), in-group index q_; fr0 holds
   // its sub-step 0 on entry and the next step's sub-step 0 on exit.
 #define H8_STEP(st_, q_, SL, STAG, COND)                                                       \
-  do {                                                                                         \
+  do {                                                                                        \
     H8_READ(fr1, SL, 1);                                                                       \
     H8_WAIT_LGKM(NF); H8_SB();                                                                 \
     H8_MFMA(fr0, 4 * (q_) + 0, 0, 2, STAG); H8_SB();                                           \
@@ -922,7 +597,7 @@ __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t 
     H8_MFMA(fr1, 4 * (q_) + 3, 1, 2, STAG); H8_SB();                                           \
   } while (0)
 #define H8_FLUSH()                                                                             \
-  do {                                                                                         \
+  do {                                                                                        \
     _Pragma("unroll") for (int a = 0; a < 2; a++)                                              \
       _Pragma("unroll") for (int b = 0; b < 2; b++)                                            \
         _Pragma("unroll") for (int r = 0; r < 16; r++) {                                       \
@@ -946,20 +621,20 @@ __device__ __forceinline__ void g8h_run(const uint16_t *__restrict__ z, int64_t 
   int64_t st = s0;
   const int64_t sfull = s0 + ((s1 - s0) / 6) * 6;
   for (; st < sfull && st + 8 < s1; st += 6) {
-    H8_STEP(st, 0, 0, !NOFLUSH, 0);
-    H8_STEP(st + 1, 1, 1, !NOFLUSH, 0);
-    H8_STEP(st + 2, 2, 2, !NOFLUSH, 0);
-    H8_STEP(st + 3, 3, 0, !NOFLUSH, 0);
-    H8_STEP(st + 4, 4, 1, !NOFLUSH, 0);
-    H8_STEP(st + 5, 5, 2, !NOFLUSH, 0);
+    H8_STEP(st, 0, 0, 1, 0);
+    H8_STEP(st + 1, 1, 1, 1, 0);
+    H8_STEP(st + 2, 2, 2, 1, 0);
+    H8_STEP(st + 3, 3, 0, 1, 0);
+    H8_STEP(st + 4, 4, 1, 1, 0);
+    H8_STEP(st + 5, 5, 2, 1, 0);
   }
   for (; st < sfull; st += 6) {
-    H8_STEP(st, 0, 0, !NOFLUSH, 1);
-    H8_STEP(st + 1, 1, 1, !NOFLUSH, 1);
-    H8_STEP(st + 2, 2, 2, !NOFLUSH, 1);
-    H8_STEP(st + 3, 3, 0, !NOFLUSH, 1);
-    H8_STEP(st + 4, 4, 1, !NOFLUSH, 1);
-    H8_STEP(st + 5, 5, 2, !NOFLUSH, 1);
+    H8_STEP(st, 0, 0, 1, 1);
+    H8_STEP(st + 1, 1, 1, 1, 1);
+    H8_STEP(st + 2, 2, 2, 1, 1);
+    H8_STEP(st + 3, 3, 0, 1, 1);
+    H8_STEP(st + 4, 4, 1, 1, 1);
+    H8_STEP(st + 5, 5, 2, 1, 1);
   }
   H8_FLUSH();
   for (int t = 0; st < s1; st++, t++) {
@@ -1005,12 +680,11 @@ __device__ __forceinline__ int g8q_swz(int rb) { return (0x78 >> (2 * (rb & 3)))
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-template <int MODE, int FL>
+template <int FL>
 __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t ld, int I, int tj, int64_t s0,
                                         int64_t s1, char *smem, f32x4 (&acc)[4][4], int32_t (&iacc)[4][4][4]) {
   constexpr int FCYC = 12 / FL;                          // fp32 chunk, in half-steps
   constexpr int HA = QSA / 2, HB = QSB / 2;
-  constexpr bool NOLOAD = MODE == 5 || MODE == 6, NOFLUSH = MODE == 6;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int wr = wv >> 1, wc = wv & 1;
@@ -1031,7 +705,7 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
 #define Q8_WAIT_LGKM(n_) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n_) : "memory")
 #define Q8_SB() __builtin_amdgcn_sched_barrier(0)
 #define Q8_ISSUE(step_, P, SL)                                                                 \
-  if (!NOLOAD) do {                                                                            \
+  do {                                                                                         \
     const int64_t ko_ = (2 * (int64_t)(step_) + (P)) * (ld >> 1);                              \
     const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(                      \
         (void *)(pa0 + ko_), (short)0, -1, 0x00020000);                                        \
@@ -1045,7 +719,7 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
   } while (0)
   // the 8 fragments (A m = 0..3, B nn = 0..3) of half P of ring slot SL
 #define Q8_READ(FR, SL, P)                                                                     \
-  if (MODE != 8) do {                                                                          \
+  do {                                                                                         \
     constexpr int oa_ = ((SL) == 2 ? 0 : (SL) * QSA) + (P) * HA;                               \
     constexpr int ob_ = (SL) * QSB + (P) * HB;                                                 \
     const uint32_t a_ = (SL) == 2 ? ba2 : ba;                                                  \
@@ -1056,7 +730,7 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
   } while (0)
   // the 16 MFMAs of a half at in-group half-step c_ (A blocks [m0, m1))
 #define Q8_MFMA(FR, c_, m0, m1, STAG)                                                          \
-  if (MODE != 7 && MODE != 8) do {                                                             \
+  do {                                                                                         \
     _Pragma("unroll") for (int m = m0; m < m1; m++)                                            \
       _Pragma("unroll") for (int nn = 0; nn < 4; nn++) {                                       \
         if ((STAG) && ((c_) % FCYC) == ((m * 4 + nn) * FCYC) / 16) {                           \
@@ -1071,14 +745,14 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
   } while (0)
   // vmcnt before barrier 1 of step st: (st, half 1) landed; younger: (st+1, *), (st+2, *)
 #define Q8_VM1(st_, COND)                                                                      \
-  do {                                                                                         \
+  do {                                                                                        \
     if (!(COND) || (st_) + 2 < s1) Q8_WAIT_VM(12);                                             \
     else if ((st_) + 1 < s1) Q8_WAIT_VM(6);                                                    \
     else Q8_WAIT_VM(0);                                                                        \
   } while (0)
   // before barrier 2: (st+1, half 0) landed; younger: (st+1, 1), (st+2, *), (st+3, 0)
 #define Q8_VM2(st_, COND)                                                                      \
-  do {                                                                                         \
+  do {                                                                                        \
     if (!(COND) || (st_) + 3 < s1) Q8_WAIT_VM(12);                                             \
     else if ((st_) + 2 < s1) Q8_WAIT_VM(9);                                                    \
     else if ((st_) + 1 < s1) Q8_WAIT_VM(3);                                                    \
@@ -1089,7 +763,7 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
   // has read half 0 (refilled with st+3) and (st, 1) is visible; barrier 2:
   // every wave has read half 1 and (st+1, 0) is visible.
 #define Q8_STEP(st_, q_, SL, STAG, COND)                                                       \
-  do {                                                                                         \
+  do {                                                                                        \
     Q8_WAIT_LGKM(0); Q8_VM1(st_, COND);                                                        \
     __builtin_amdgcn_s_barrier(); Q8_SB();                                                     \
     if (!(COND) || (st_) + 3 < s1) Q8_ISSUE((st_) + 3, 0, SL);                                 \
@@ -1104,7 +778,7 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
     Q8_MFMA(F1, 2 * (q_) + 1, 0, 4, STAG); Q8_SB();                                            \
   } while (0)
 #define Q8_FLUSH()                                                                             \
-  do {                                                                                         \
+  do {                                                                                        \
     _Pragma("unroll") for (int a = 0; a < 4; a++)                                              \
       _Pragma("unroll") for (int b = 0; b < 4; b++)                                            \
         _Pragma("unroll") for (int r = 0; r < 4; r++) {                                        \
@@ -1128,20 +802,20 @@ __device__ __forceinline__ void g8q_run(const uint16_t *__restrict__ z, int64_t 
   int64_t st = s0;
   const int64_t sfull = s0 + ((s1 - s0) / 6) * 6;
   for (; st < sfull && st + 8 < s1; st += 6) {
-    Q8_STEP(st, 0, 0, !NOFLUSH, 0);
-    Q8_STEP(st + 1, 1, 1, !NOFLUSH, 0);
-    Q8_STEP(st + 2, 2, 2, !NOFLUSH, 0);
-    Q8_STEP(st + 3, 3, 0, !NOFLUSH, 0);
-    Q8_STEP(st + 4, 4, 1, !NOFLUSH, 0);
-    Q8_STEP(st + 5, 5, 2, !NOFLUSH, 0);
+    Q8_STEP(st, 0, 0, 1, 0);
+    Q8_STEP(st + 1, 1, 1, 1, 0);
+    Q8_STEP(st + 2, 2, 2, 1, 0);
+    Q8_STEP(st + 3, 3, 0, 1, 0);
+    Q8_STEP(st + 4, 4, 1, 1, 0);
+    Q8_STEP(st + 5, 5, 2, 1, 0);
   }
   for (; st < sfull; st += 6) {
-    Q8_STEP(st, 0, 0, !NOFLUSH, 1);
-    Q8_STEP(st + 1, 1, 1, !NOFLUSH, 1);
-    Q8_STEP(st + 2, 2, 2, !NOFLUSH, 1);
-    Q8_STEP(st + 3, 3, 0, !NOFLUSH, 1);
-    Q8_STEP(st + 4, 4, 1, !NOFLUSH, 1);
-    Q8_STEP(st + 5, 5, 2, !NOFLUSH, 1);
+    Q8_STEP(st, 0, 0, 1, 1);
+    Q8_STEP(st + 1, 1, 1, 1, 1);
+    Q8_STEP(st + 2, 2, 2, 1, 1);
+    Q8_STEP(st + 3, 3, 0, 1, 1);
+    Q8_STEP(st + 4, 4, 1, 1, 1);
+    Q8_STEP(st + 5, 5, 2, 1, 1);
   }
   Q8_FLUSH();
   for (int t = 0; st < s1; st++, t++) {
@@ -1230,6 +904,9 @@ __device__ __forceinline__ void g8q_atomics_wide(int32_t (&iacc)[4][4][4], int I
 // small cohort (fewer tile groups than XCDs) splits K eight ways; a large one
 // gives every XCD whole tile groups over the full K range, so each output tile
 // is flushed with int64 atomics only once per int32-exact unit (sps_max steps).
+// MODE 0 production; 9 the compile-only no-flush skeleton of GRID_ISA_PROBE.
+// LAY 1: row-major panel, quad-row ring (g8_run); K-blocked panel (BL): LAY 3
+// the half-split ring with 32x32x16 MFMAs (g8h_run), LAY 4 with 16x16x32 (g8q_run).
 template <int MODE, bool BL, int FL, int LAY>
 __global__ __launch_bounds__(512, 1) void k_gram8(const uint16_t *__restrict__ z, int64_t ld,
                                                   const int32_t *__restrict__ tiles, int ntiles, int kc, int kx,
@@ -1237,6 +914,8 @@ __global__ __launch_bounds__(512, 1) void k_gram8(const uint16_t *__restrict__ z
                                                   int64_t np_, unsigned long long *__restrict__ gram,
                                                   unsigned *__restrict__ rounds, int dyn,
                                                   int32_t *__restrict__ part, GramXoff xoff, int gs) {
+  static_assert(MODE == 0 || MODE == 9, "MODE 9 is the no-flush ISA probe");
+  static_assert((LAY == 1 && !BL) || ((LAY == 3 || LAY == 4) && BL), "LAY 1: row-major; LAY 3, 4: K-blocked");
   __shared__ __attribute__((aligned(1024))) char smem[3 * SLOT3];
   __shared__ int64_t s_unit;
   const int nwg = gridDim.x;
@@ -1279,8 +958,8 @@ __global__ __launch_bounds__(512, 1) void k_gram8(const uint16_t *__restrict__ z
     const int32_t tv = tiles[t];
     // wave-uniform values the compiler cannot prove uniform (u may come from
     // LDS): readfirstlane keeps them, and the K-loop bounds, in SGPRs
-    const int I = __builtin_amdgcn_readfirstlane(MODE == 1 ? 0 : tv >> 16);
-    const int tj = __builtin_amdgcn_readfirstlane(MODE == 1 ? 0 : tv & 0xFFFF);
+    const int I = __builtin_amdgcn_readfirstlane(tv >> 16);
+    const int tj = __builtin_amdgcn_readfirstlane(tv & 0xFFFF);
     const int64_t s0 = uniform64(xs0 + xlen * c / kc), s1 = uniform64(xs0 + xlen * (c + 1) / kc);
     // pace: wait (bounded) until the XCD's round ru - lag is complete
     if (ru >= lag && threadIdx.x == 0) {
@@ -1302,7 +981,7 @@ __global__ __launch_bounds__(512, 1) void k_gram8(const uint16_t *__restrict__ z
           for (int b = 0; b < 4; b++)
 #pragma unroll
             for (int r = 0; r < 4; r++) { acc[a][b][r] = 0.0f; iacc[a][b][r] = 0; }
-        g8q_run<MODE, FL>(z, ld, I, tj, s0, s1, smem, acc, iacc);
+        g8q_run<FL>(z, ld, I, tj, s0, s1, smem, acc, iacc);
         if constexpr (MODE != 9) {
           if (dyn & 2) g8q_atomics_wide(iacc, I, tj, np_, gram);
           else g8q_atomics(iacc, I, tj, np_, gram);
@@ -1312,9 +991,8 @@ __global__ __launch_bounds__(512, 1) void k_gram8(const uint16_t *__restrict__ z
       f32x16 acc[2][2];
       int32_t iacc[2][2][16];
       g6_zero<2>(acc, iacc);
-      if constexpr (LAY == 2) g8h_run<MODE, BL, FL>(z, ld, I, tj, s0, s1, smem, acc, iacc);
-      else if constexpr (LAY == 3) g8h_run<MODE, BL, FL, BL>(z, ld, I, tj, s0, s1, smem, acc, iacc);
-      else g8_run<MODE, BL, FL, LAY == 1>(z, ld, I, tj, s0, s1, smem, acc, iacc);
+      if constexpr (LAY == 3) g8h_run<FL>(z, ld, I, tj, s0, s1, smem, acc, iacc);
+      else g8_run<FL>(z, ld, I, tj, s0, s1, smem, acc, iacc);
       if constexpr (MODE == 9) {
         // no-flush ISA probe (compile-only, tools/isa_barriers.py --probe): the
         // tile's results are dropped, so every MFMA is dead code
@@ -1331,8 +1009,12 @@ __global__ __launch_bounds__(512, 1) void k_gram8(const uint16_t *__restrict__ z
 
 #ifdef GRID_ISA_PROBE
 // Compile-only (never linked into a library): the round-2 no-flush timing probe
-// of the half-split ring, rebuilt so its ISA can be compared with production
-// k_gram8<0, true, 1, 3> (tools/isa_barriers.py --probe).
+// of the half-split ring, rebuilt so its ISA can be compared with the flushing
+// k_gram8<0, true, 1, 3> of the same compile (tools/isa_barriers.py --probe).
+template __global__ void k_gram8<0, true, 1, 3>(const uint16_t *__restrict__, int64_t, const int32_t *__restrict__,
+                                                int, int, int, int64_t, int, int, int64_t,
+                                                unsigned long long *__restrict__, unsigned *__restrict__, int,
+                                                int32_t *__restrict__, GramXoff, int);
 template __global__ void k_gram8<9, true, 1, 3>(const uint16_t *__restrict__, int64_t, const int32_t *__restrict__,
                                                 int, int, int, int64_t, int, int, int64_t,
                                                 unsigned long long *__restrict__, unsigned *__restrict__, int,
@@ -2052,7 +1734,7 @@ extern "C" {
 // row ranges re-use their uploaded lists instead of re-uploading them (a host
 // sync) every time, and the whole triangle of any np fits.
 static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_t nsteps, int64_t ld,
-                        int64_t q2, int64_t sps_max, bool blocked, int mode, int64_t *d_gram, int ti0, int ti1,
+                        int64_t q2, int64_t sps_max, bool blocked, int64_t *d_gram, int ti0, int ti1,
                         int64_t ldg) {
   const int nt = (int)(np_ / BM);
   int nt6 = 0;
@@ -2081,7 +1763,7 @@ static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_
       ts.cap = (size_t)nt6;
     }
     ts.host = new int32_t[nt6];
-    // tile_blocked6 order (groups of GI6 row tiles x GJ6 column tiles),
+    // super-block order (groups of GI6 row tiles x GJ6 column tiles, see GI6),
     // enumerated incrementally from the range's first row tile
     int t = 0;
     for (int i0 = ti0; i0 < ti1; i0 += GI6) {
@@ -2104,11 +1786,7 @@ static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_
   const int32_t *d_tiles = ctx->tiles[slot].dev;
   unsigned *rounds = (unsigned *)((char *)ctx->aux + GRID_AUX_BYTES / 2);
   HIPCHK(hipMemsetAsync(rounds, 0, (128 + 8 * 16) * 4, ctx->stream));   // round and unit counters
-  int per = ctx->ncu >= 8 ? ctx->ncu / 8 : 1;
-  // tools A/B (GRID_GRAM_PER: workgroups per XCD below the CU count): how the
-  // feed rate per CU changes with the number of CUs streaming at once
-  const char *pere = GRID_AB_KNOB("GRID_GRAM_PER");
-  if (pere && atoi(pere) >= 1 && atoi(pere) < per) per = atoi(pere);
+  const int per = ctx->ncu >= 8 ? ctx->ncu / 8 : 1;   // workgroups per XCD
   // tiles per group (tools A/B GRID_GRAM_GS, default per): fewer than per deals
   // a small cohort's tiles to more groups, so that every XCD can take whole
   // groups over the full K range (kx = 1) and all XCDs stream the same K-steps
@@ -2122,8 +1800,7 @@ static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_
   // CU: ~25-50 us, i.e. tens of K-steps -- without it, short K ranges were cut
   // into hundreds of units and the flushes doubled the launch); the fewest
   // K-ranges within 1 % of the best cost, then the chunk count that wastes least
-  const char *ufe = GRID_AB_KNOB("GRID_GRAM_UF");
-  const double UF = ufe ? atof(ufe) : 40.0;
+  const double UF = 40.0;
   int64_t bkx = 8, bkc = 1;
   double bcost = -1.0;
   for (int kx = 8; kx >= 1; kx >>= 1) {
@@ -2165,38 +1842,14 @@ static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_
   REQUIRE(ceil_div(ceil_div(nsteps, bkx), bkc) <= sps_max, "Gram K chunk exceeds the int32-exact length");
   // fp32 chunks of 384 products while 384 qmax^2 <= 2^24 (qmax <= 209), else 192
   const int fl = 384 * q2 <= (1ll << 24) ? 1 : 2;
-#ifdef GRID_PROBES
-#define G8_PICK(BLV, QLV)                                                                       \
-  (mode == 5 ? (fl == 1 ? k_gram8<5, BLV, 1, QLV> : k_gram8<5, BLV, 2, QLV>)                    \
-   : mode == 6 ? (fl == 1 ? k_gram8<6, BLV, 1, QLV> : k_gram8<6, BLV, 2, QLV>)                  \
-   : mode == 1 ? (fl == 1 ? k_gram8<1, BLV, 1, QLV> : k_gram8<1, BLV, 2, QLV>)                  \
-   : mode == 7 ? k_gram8<7, BLV, 1, QLV> : mode == 8 ? k_gram8<8, BLV, 1, QLV>                  \
-   : (fl == 1 ? k_gram8<0, BLV, 1, QLV> : k_gram8<0, BLV, 2, QLV>))
-#define G8_PICK1(BLV, QLV)                                                                      \
-  (mode == 5 ? k_gram8<5, BLV, 1, QLV> : mode == 6 ? k_gram8<6, BLV, 1, QLV>                    \
-   : mode == 1 ? k_gram8<1, BLV, 1, QLV> : mode == 7 ? k_gram8<7, BLV, 1, QLV>                  \
-   : mode == 8 ? k_gram8<8, BLV, 1, QLV> : k_gram8<0, BLV, 1, QLV>)
-#else
-  (void)mode;
-#define G8_PICK(BLV, QLV) (fl == 1 ? k_gram8<0, BLV, 1, QLV> : k_gram8<0, BLV, 2, QLV>)
-#define G8_PICK1(BLV, QLV) k_gram8<0, BLV, 1, QLV>
-#endif
-  // LDS image.  K-blocked panel ([kpad/KBW][np][KBW], KBW = 32): the half-split
-  // ring (LAY 3).  Row-major panel (timing A/B, results identical): 1 quad-row
-  // pieces (default), 2 half-split ring, 0 the earlier pair-row pieces (GRID_GRAM_QL)
-  const char *qe = GRID_AB_KNOB("GRID_GRAM_QL");
-  const int lay = qe ? atoi(qe) : 1;
-  REQUIRE(lay >= 0 && lay <= 2, "GRID_GRAM_QL must be 0, 1 or 2");
+  // Row-major panel: the quad-row ring (LAY 1).  K-blocked panel
+  // ([kpad/KBW][np][KBW], KBW = 32), half-split ring: 16x16x32 MFMAs (LAY 4) for
+  // 384-product fp32 chunks (28.96 vs 29.83 ms at config 2, 887 vs 909 ms at the
+  // config-3 chunk, r03ae), 32x32x16 (LAY 3) for FL = 2, where LAY 4's loop spills.
   static_assert(KBW == BK / 2, "k_gram8's K-blocked path reads 32-wide K-blocks");
-  // K-blocked: 16x16x32 MFMAs (LAY 4, the default for 384-product fp32 chunks:
-  // 28.96 vs 29.83 ms at config 2, 887 vs 909 ms at the config-3 chunk, r03ae)
-  // or 32x32x16 (LAY 3: FL = 2, where LAY 4's loop spills; tools A/B GRID_GRAM_Q16=0)
-  const char *q16e = GRID_AB_KNOB("GRID_GRAM_Q16");
-  const bool q16 = blocked && fl == 1 && (q16e ? atoi(q16e) != 0 : true);
-  auto kern = blocked ? (q16 ? G8_PICK1(true, 4) : G8_PICK(true, 3))
-                      : (lay == 2 ? G8_PICK(false, 2) : lay == 1 ? G8_PICK(false, 1) : G8_PICK(false, 0));
-#undef G8_PICK
-#undef G8_PICK1
+  auto kern = blocked ? (fl == 1 ? k_gram8<0, true, 1, 4> : k_gram8<0, true, 2, 3>)
+                      : (fl == 1 ? k_gram8<0, false, 1, 1> : k_gram8<0, false, 2, 1>);
+  const bool q16 = blocked && fl == 1;   // LAY 4: the 16x16 tile has no partial-mode flush
   // partial mode (GRID_GRAM_PART_MB > 0: while the slots fit that many MiB; off by default): plain
   // int32 stores of each unit's tile into its own slot, one reduction launch
   // after the Gram, in place of the int64 atomics (the atomics were not what bounds the Gram)
@@ -2215,7 +1868,7 @@ static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_
       xoff.x[x] = tot;
       tot += ngx > 0 ? ((ngx - 1) * gs + lastsz) * bkc : 0;
     }
-    if (mode == 0 && !q16 && gs == per && part_cap > 0 && ldg == np_ && ti0 == 0 && tot * (int64_t)(BM3 * BN3 * 4) <= part_cap) {
+    if (!q16 && gs == per && part_cap > 0 && ldg == np_ && ti0 == 0 && tot * (int64_t)(BM3 * BN3 * 4) <= part_cap) {
       void *sp = nullptr;
       int rc = grid_scratch(ctx, (size_t)tot * BM3 * BN3 * 4, &sp);
       if (rc) return rc;
@@ -2235,19 +1888,6 @@ static int launch_gram8(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_
   return GRID_OK;
 }
 
-// Product builds run the production kernels only; the tools build
-// (make probes: -DGRID_PROBES, libgridhip_probes.so) maps GRID_GRAM_VARIANT to
-// the A/B kernels and the timing probes of tools/bench_gram.py (the probes
-// give wrong results by design).
-static int gram_variant() {
-#ifdef GRID_PROBES
-  const char *ve = getenv("GRID_GRAM_VARIANT");
-  return ve ? atoi(ve) : 21;
-#else
-  return 21;
-#endif
-}
-
 int grid_knn_gram(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_t kpad, int64_t ld,
                   int32_t qmax, int64_t *d_gram) {
   REQUIRE(ctx && d_zb && d_gram, "bad args");
@@ -2264,33 +1904,8 @@ int grid_knn_gram(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_t kpad
   int64_t sps_max = ((1ll << 31) - 1) / (q2 * BK);
   const int nt = (int)(np_ / BM);
   const int ntiles = nt * (nt + 1) / 2;
-  const int variant = gram_variant();
-  if (variant >= 21 && np_ % BM3 == 0)
-    return launch_gram8(ctx, d_zb, np_, nsteps, ld, q2, sps_max, false, variant == 22 ? 5 : variant == 23 ? 6
-                        : variant == 24 ? 1 : 0, d_gram, 0, (int)(np_ / BM3), np_);
-#ifdef GRID_PROBES
-  if (variant >= 6 && np_ % BM3 == 0) {
-    // 256x128 tiles; 4-step fp32 chunks stay exact: 4 * 64 * qmax^2 < 2^24 for qmax <= 256
-    const int ni = (int)(np_ / BM3);
-    int nt6 = 0;
-    for (int i = 0; i < ni; i++) nt6 += nt - 2 * i;
-    int64_t sps6 = ceil_div(nsteps, ceil_div(256, nt6));
-    if (sps6 > sps_max) sps6 = sps_max;
-    const int64_t nsl6 = ceil_div(nsteps, sps6);
-    REQUIRE(nsl6 * nt6 < (1ll << 31), "too many work items");
-    // 6 production; 8, 14, 15 timing probes (wrong results, see k_gram6); 11 without the XCD remap
-    // 16-18: the same with 6-step flush groups (qmax <= 209); 18 = no loads and no flush
-    const bool g6ok = 384 * q2 <= (1ll << 24);
-    auto kern = variant == 8 ? k_gram6<2, 1, 2, 4> : variant == 11 ? k_gram6<3, 1, 2, 4>
-              : variant == 14 ? k_gram6<4, 1, 2, 4> : variant == 15 ? k_gram6<5, 1, 2, 4>
-              : (variant == 16 && g6ok) ? k_gram6<0, 1, 2, 6> : (variant == 17 && g6ok) ? k_gram6<5, 1, 2, 6>
-              : (variant == 18 && g6ok) ? k_gram6<6, 1, 2, 6> : k_gram6<0, 1, 2, 4>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nsl6 * nt6)), dim3(512), 0, ctx->stream, d_zb, ld, nt, ni, nt6,
-                       nsteps, (int)sps6, np_, (unsigned long long *)d_gram);
-    LAUNCHCHK();
-    return GRID_OK;
-  }
-#endif
+  if (np_ % BM3 == 0)
+    return launch_gram8(ctx, d_zb, np_, nsteps, ld, q2, sps_max, false, d_gram, 0, (int)(np_ / BM3), np_);
   {
     // np % 256 != 0: 128x128 tiles, one K-slice per workgroup
     int64_t target_slices = ceil_div(2048, ntiles);
@@ -2301,7 +1916,7 @@ int grid_knn_gram(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_t kpad
     const int64_t nwg = nslices * ntiles;
     REQUIRE(nwg < (1ll << 31), "too many work items");
     hipLaunchKernelGGL(k_gram_dma, dim3((unsigned)nwg), dim3(NT), 0, ctx->stream, d_zb, ld, nt, ntiles, nsteps,
-                       (int)sps, fs, np_, (unsigned long long *)d_gram, variant == 4 ? 1 : 0);
+                       (int)sps, fs, np_, (unsigned long long *)d_gram);
   }
   LAUNCHCHK();
   return GRID_OK;
@@ -2317,11 +1932,7 @@ int grid_knn_gram_kb(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_t k
   if (kpad == 0) return GRID_OK;
   const int64_t q2 = (int64_t)(qmax > 0 ? qmax : 1) * (qmax > 0 ? qmax : 1);
   const int64_t sps_max = ((1ll << 31) - 1) / (q2 * BK);
-  const int variant = gram_variant();
-  const int mode = variant == 22 ? 5 : variant == 23 ? 6 : variant == 24 ? 1 : variant == 25 ? 7
-                 : variant == 26 ? 8 : 0;
-  return launch_gram8(ctx, d_zb, np_, kpad / BK, np_ * BK, q2, sps_max, true, mode, d_gram, 0, (int)(np_ / BM3),
-                      np_);
+  return launch_gram8(ctx, d_zb, np_, kpad / BK, np_ * BK, q2, sps_max, true, d_gram, 0, (int)(np_ / BM3), np_);
 }
 
 int grid_knn_gram_kb_rows(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int64_t kpad, int32_t qmax, int64_t row0,
@@ -2341,7 +1952,7 @@ int grid_knn_gram_kb_rows(grid_ctx *ctx, const uint16_t *d_zb, int64_t np_, int6
   // the kernel adds tile element (row, col) at base + row * ld + col: the
   // base sits row0 * (ld + 1) elements before d_out (never dereferenced there)
   int64_t *base = (int64_t *)((uintptr_t)d_out - (uintptr_t)(row0 * (ld + 1)) * sizeof(int64_t));
-  return launch_gram8(ctx, d_zb, np_, kpad / BK, np_ * BK, q2, sps_max, true, 0, base, (int)(row0 / BM3),
+  return launch_gram8(ctx, d_zb, np_, kpad / BK, np_ * BK, q2, sps_max, true, base, (int)(row0 / BM3),
                       (int)((row0 + nrows) / BM3), ld);
 }
 

@@ -131,7 +131,7 @@ def test_knn_random(dev, n, r, k, qmax, seed):
 
 def test_gram_exact_worst_case(dev):
     """bf16 MFMA + fp32 partials are exact at the integer bounds (all |q| = qmax):
-    6-step fp32 chunks up to qmax 209 (k_gram8), 4-step chunks above (k_gram7)."""
+    6-step fp32 chunks up to qmax 209 (k_gram8), 3-step chunks above (both k_gram8)."""
     from grid_amd._abi import call
     for qmax in (200, 209, 210, 256):
         rng = np.random.default_rng(qmax)
