@@ -95,6 +95,7 @@ _SIGS = {
     "grid_knn_gather_i32": [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp],
     "grid_knn_gather_f64": [_vp, _vp, _i64, _i64, _vp, _i64, _f64, _vp],
     "grid_dipcn": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i32)],
+    "grid_dipcn_loci": [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "grid_hi_levels": [_i64, _vp, _vp, _vp, _vp, C.POINTER(_i32)],
     "grid_hi_pack": [_i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "grid_hi_phase": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,

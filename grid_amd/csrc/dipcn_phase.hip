@@ -36,6 +36,99 @@ __global__ void k_dipcn(int64_t n, const double *__restrict__ reads, const uint8
   valid[i] = 1;
 }
 
+// k_dipcn for every locus of a table in one launch.  reads is locus-minor
+// [U][ldl] (NaN = the id has no count at that locus), so the neighbour lists
+// are walked once per sample with the loci across a wave's lanes: one workgroup
+// per sample, its DL_WAVES waves striding over 64-locus chunks.  nbr[i][t] and
+// nscale[i][t] are the same for the whole wave (the wave id goes through
+// readfirstlane and the loop leaves on a wave-wide vote, so t and the list
+// reads stay on the scalar unit) and every gather reads one contiguous 512-byte
+// piece of row j.  Lanes differ only through presence: a lane is predicated by
+// `has && count < n_nbr` and the wave leaves the list once no lane is pending.
+// Each (i, l) runs k_dipcn's operations in k_dipcn's order.
+constexpr int DL_WAVES = 4;
+constexpr int DL_UNROLL = 4;      // list entries whose gathers are in flight together
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DL_CONST __attribute__((address_space(4)))
+#else
+#define DL_CONST
+#endif
+
+__global__ __launch_bounds__(64 * DL_WAVES) void k_dipcn_loci(
+    int64_t n_loci, int64_t ldl, int64_t u, const double *__restrict__ reads, const double *__restrict__ scale,
+    const int32_t *__restrict__ nbr, const double *__restrict__ nscale, const int32_t *__restrict__ ncnt,
+    int64_t ld, int64_t n_nbr, double *__restrict__ out, uint8_t *__restrict__ valid,
+    int32_t *__restrict__ zerodiv, uint8_t *__restrict__ missed) {
+  const int64_t i = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int32_t c = ncnt[i] < ld ? ncnt[i] : (int32_t)ld;
+  // the lists are read-only for the whole launch: read through the constant
+  // address space, a uniform address there is a scalar load whatever the
+  // kernel stores elsewhere (the byte stores to `missed` otherwise turn the
+  // list reads into vector loads that wait on the gathers' counter)
+  const DL_CONST int32_t *nb = (const DL_CONST int32_t *)(nbr + i * ld);
+  const DL_CONST double *nsc = (const DL_CONST double *)(nscale + i * ld);
+  const double s = scale[i];
+  const double qnan = __builtin_nan("");
+  for (int64_t l0 = (int64_t)wave * 64; l0 < ldl; l0 += 64 * DL_WAVES) {
+    const int64_t l = l0 + lane;
+    const bool in = l < ldl;                     // the row's padding is written too (valid = 0)
+    const double ri = (in && l < n_loci) ? reads[i * ldl + l] : qnan;
+    const bool has = ri == ri;
+    bool live = has, zd = false;
+    double total = 0.0;
+    int64_t count = 0;
+    for (int32_t t0 = 0; t0 < c; t0 += DL_UNROLL) {
+      if (__ballot(live && count < n_nbr) == 0) break;
+      int32_t j[DL_UNROLL];
+      double ns[DL_UNROLL], x[DL_UNROLL];
+#pragma unroll
+      for (int e = 0; e < DL_UNROLL; e++) {
+        const int32_t t = t0 + e < c ? t0 + e : c - 1;
+        j[e] = nb[t];
+        ns[e] = nsc[t];
+        if (t0 + e >= c || j[e] >= u) j[e] = -1;   // the list's end; never read past the matrix
+      }
+#pragma unroll
+      for (int e = 0; e < DL_UNROLL; e++)
+        x[e] = (j[e] >= 0 && has) ? reads[(int64_t)j[e] * ldl + l] : qnan;
+#pragma unroll
+      for (int e = 0; e < DL_UNROLL; e++) {
+        if (j[e] < 0) continue;
+        const bool pending = live && count < n_nbr;
+        const bool present = x[e] == x[e];
+        if (pending && !present && missed) missed[(int64_t)j[e] * ldl + l] = 1;
+        if (pending && present) {
+          if (ns[e] == 0.0) {                    // Python: ZeroDivisionError
+            zd = true;
+            live = false;
+          } else {
+            total = total + x[e] / ns[e];
+            count++;
+          }
+        }
+      }
+    }
+    bool ok = live && count > 0;
+    double v = 0.0;
+    if (ok) {
+      const double mean = total / (double)count;
+      if (s == 0.0 || mean == 0.0) {
+        zd = true;
+        ok = false;
+      } else {
+        v = (ri / s) / mean;
+      }
+    }
+    if (zd) zerodiv[l] = 1;                      // every writer stores the same 1
+    if (in) {
+      out[i * ldl + l] = v;
+      valid[i * ldl + l] = ok ? 1 : 0;
+    }
+  }
+}
+
 __device__ __forceinline__ void nbr_means(int64_t i, const double *hap, const int64_t *off,
                                           const int32_t *nbr, const double *w, double ws[2],
                                           double wv[2]) {
@@ -1063,6 +1156,23 @@ int grid_dipcn(grid_ctx *ctx, int64_t n, const double *d_reads, const uint8_t *d
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *h_zerodiv = *(int32_t *)ctx->pinned;
   }
+  return GRID_OK;
+}
+
+int grid_dipcn_loci(grid_ctx *ctx, int64_t n, int64_t u, int64_t n_loci, int64_t ldl, const double *d_reads,
+                    const double *d_scale, const int32_t *d_nbr, const double *d_nscale, const int32_t *d_ncnt,
+                    int64_t ld, int64_t n_nbr, double *d_out, uint8_t *d_valid, int32_t *d_zerodiv,
+                    uint8_t *d_missed) {
+  REQUIRE(ctx && n >= 0 && u >= n && n_loci >= 0 && ld >= 0, "bad args");
+  REQUIRE(ldl >= n_loci && ldl % 8 == 0, "ldl must be n_loci rounded up to a multiple of 8 or more");
+  REQUIRE(n <= 0x7fffffff && u <= 0x7fffffff, "more than 2^31 - 1 samples");
+  if (n_loci > 0) HIPCHK(hipMemsetAsync(d_zerodiv, 0, (size_t)n_loci * sizeof(int32_t), ctx->stream));
+  if (d_missed && u > 0 && ldl > 0) HIPCHK(hipMemsetAsync(d_missed, 0, (size_t)u * (size_t)ldl, ctx->stream));
+  if (n == 0 || ldl == 0) return GRID_OK;
+  REQUIRE(d_reads && d_scale && d_nbr && d_nscale && d_ncnt && d_out && d_valid && d_zerodiv, "null pointer");
+  hipLaunchKernelGGL(k_dipcn_loci, dim3((unsigned)n), dim3(64 * DL_WAVES), 0, ctx->stream, n_loci, ldl, u, d_reads,
+                     d_scale, d_nbr, d_nscale, d_ncnt, ld, n_nbr, d_out, d_valid, d_zerodiv, d_missed);
+  LAUNCHCHK();
   return GRID_OK;
 }
 

@@ -9,7 +9,7 @@ stays here, on a handful of values read back from the device.
 Reference correspondence (paths under /root/reference):
   normalize_stats / select   grid/utils/normalize_mosdepth.py:120, 419-499
   knn_*                      grid/utils/find_neighbors.py:57-65, 128-227
-  dipcn                      grid/utils/compute_dipcn.py:62-88
+  dipcn / dipcn_loci         grid/utils/compute_dipcn.py:62-88 (one locus / every locus of a table)
   phase                      grid/utils/hi_inference.py:175-250
 """
 from __future__ import annotations
@@ -303,6 +303,72 @@ def dipcn(dev: Device, reads: np.ndarray, has: np.ndarray, scale: np.ndarray, nb
     if zd.value:
         raise ZeroDivisionError("float division by zero")
     return out.numpy()[:n], valid.numpy()[:n].astype(bool)
+
+
+DIPCN_LOCI_HBM_FRACTION = 0.5    # of the free HBM: the per-group matrices of dipcn_loci
+
+
+def dipcn_loci(dev: Device, reads_UL: np.ndarray, scale: np.ndarray, nbr: np.ndarray, nscale: np.ndarray,
+               ncnt: np.ndarray, n_nbr: int, n_rows: int, group: int | None = None):
+    """dipcn for every locus of a table (grid_dipcn_loci; BASELINE config 5).
+
+    ``reads_UL`` [U][L or more], locus-minor: row = id of the universe (the
+    ``n_rows`` neighbour-file rows first), column = locus, NaN = no count for
+    that id at that locus; L = its column count (all-NaN padding columns just
+    give loci without output).  scale, nbr, nscale, ncnt: dipcn's list arrays,
+    uploaded once and shared by every locus.  The loci run in groups of
+    ``group``; by default all in one launch unless the reads, out, valid and
+    missed matrices of a group would exceed DIPCN_LOCI_HBM_FRACTION of the
+    free HBM.  Returns (out [n][L], valid [n][L] bool, zerodiv [L] bool --
+    that locus is the reference's ZeroDivisionError, its columns are not to be
+    used -- and missed [L]: how many ids the reference's ``missing_ids`` would
+    hold for that locus)."""
+    reads_UL = np.asarray(reads_UL, dtype=F8)
+    if reads_UL.ndim != 2:
+        raise ValueError("reads_UL must be [U][L]")
+    u, nl = reads_UL.shape
+    n = int(n_rows)
+    nbr = np.ascontiguousarray(nbr, dtype=I4)
+    ld = nbr.shape[1] if nbr.ndim == 2 else 0
+    ncnt = np.ascontiguousarray(ncnt, dtype=I4)
+    if not 0 <= n <= u or len(ncnt) < n or len(scale) < n or (ld and nbr.shape[0] < n):
+        raise ValueError("dipcn_loci: n_rows exceeds the universe or the list arrays")
+    if ld and np.shape(nscale) != nbr.shape:
+        raise ValueError("dipcn_loci: nbr and nscale differ in shape")
+    if n and (ncnt[:n].max() > ld or (ld and nbr[:n].max() >= u)):
+        raise ValueError("dipcn_loci: a neighbour count or index exceeds its array")
+    out, valid = np.zeros((n, nl), F8), np.zeros((n, nl), bool)
+    zerodiv, missed = np.zeros(nl, bool), np.zeros(nl, I8)
+    if n == 0 or nl == 0:
+        return out, valid, zerodiv, missed
+    if group is None:
+        per_locus = u * (8 + 1) + n * (8 + 1)            # reads + missed, out + valid
+        fit = int(dev.mem_info()[0] * DIPCN_LOCI_HBM_FRACTION) // max(per_locus, 1)
+        group = nl if fit >= nl else max(64, fit // 64 * 64)
+    group = max(1, int(group))
+    d_scale, d_nbr, d_nsc, d_cnt = (dev.upload(np.ascontiguousarray(a)) for a in
+                                    (np.asarray(scale, F8), nbr if ld else np.full((n, 1), -1, I4),
+                                     np.asarray(nscale, F8) if ld else np.zeros((n, 1), F8), ncnt))
+    for l0 in range(0, nl, group):
+        g = min(group, nl - l0)
+        ldl = pad_to(g, 8)
+        if l0 == 0 and g == nl and ldl == nl and reads_UL.flags.c_contiguous:
+            sub = reads_UL                               # the caller's padded matrix as it is
+        else:
+            sub = np.full((u, ldl), np.nan, F8)
+            sub[:, :g] = reads_UL[:, l0:l0 + g]
+        d_reads = dev.upload(sub)
+        d_out, d_valid = dev.alloc((n, ldl), F8), dev.alloc((n, ldl), U1)
+        d_zd, d_miss = dev.alloc(g, I4), dev.alloc((u, ldl), U1)
+        call("grid_dipcn_loci", dev.ctx, n, u, g, ldl, d_reads.ptr, d_scale.ptr, d_nbr.ptr, d_nsc.ptr, d_cnt.ptr,
+             max(ld, 1), int(n_nbr), d_out.ptr, d_valid.ptr, d_zd.ptr, d_miss.ptr)
+        out[:, l0:l0 + g] = d_out.numpy()[:, :g]
+        valid[:, l0:l0 + g] = d_valid.numpy()[:, :g] != 0
+        zerodiv[l0:l0 + g] = d_zd.numpy() != 0
+        missed[l0:l0 + g] = d_miss.numpy()[:, :g].sum(axis=0, dtype=I8)
+        for b in (d_reads, d_out, d_valid, d_zd, d_miss):
+            b.free()
+    return out, valid, zerodiv, missed
 
 
 # ------------------------------------------------------------------ step 7 --

@@ -19,8 +19,11 @@ def _oos(console, what):
 def run_wgs_pipeline(console=False, config=None, keep_buffers=False, **args):
     """Steps 4-7 as the reference's run_wgs_pipeline (:9-103).  Under
     torch.distributed.run (WORLD_SIZE > 1) every rank runs this and steps 4-5
-    use every GPU of the job (utils/dist_step4.py); steps 6-7 run on rank 0
-    (a loci table's loci are dealt over the ranks).  ``keep_buffers``: keep
+    use every GPU of the job (utils/dist_step4.py); steps 6-7 run on rank 0,
+    unless their section names a ``loci_file`` (BASELINE config 5): that step
+    then runs once per region of the table -- step 6 in one batched launch
+    over all regions, writing the per-locus dipCN files step 7's loci mode
+    reads by default -- with the loci dealt over the ranks.  ``keep_buffers``: keep
     the device ingest's buffers cached for the process's next run instead of
     releasing them at the end (their release holds the HIP runtime ~0.5 s)."""
     from .device import deferred_release
@@ -67,8 +70,11 @@ def _run(console, config):
 
     if cfg["compute_diploid_genotypes"].get("run") == True:  # noqa: E712
         try:
-            from .utils.compute_dipcn import compute_diploid_genotypes
-            compute_diploid_genotypes(cfg, console)
+            from .utils.compute_dipcn import compute_diploid_genotypes, compute_diploid_genotypes_loci
+            if cfg["compute_diploid_genotypes"].get("loci_file"):
+                compute_diploid_genotypes_loci(cfg, console)     # many regions (BASELINE config 5)
+            else:
+                compute_diploid_genotypes(cfg, console)
         except Exception as e:
             log(console, f"Failed to compute diploid CNV calls: {e}", style="danger")
 

@@ -438,6 +438,23 @@ int grid_dipcn(grid_ctx *ctx, int64_t n, const double *d_reads, const uint8_t *d
                const double *d_scale, const int32_t *d_nbr, const double *d_nbr_scale,
                const int32_t *d_nbr_cnt, int64_t ld, int64_t n_nbr, double *d_out,
                uint8_t *d_valid, int32_t *h_zerodiv);
+/* grid_dipcn for every locus of a loci table in one launch (the list arrays
+ * d_scale, d_nbr, d_nbr_scale, d_nbr_cnt are shared by all loci, as above).
+ * d_reads [u][ldl], locus-minor: row = id of the universe (the n neighbour-file
+ * rows first), column = locus, NaN = no count for that id at that locus (the
+ * columns n_loci..ldl-1 are padding and are not read); ldl = n_loci rounded up
+ * to a multiple of 8.  A neighbour index outside [0, u) is skipped.
+ * Every (i, l) is grid_dipcn's computation for locus l: d_out [n][ldl],
+ * d_valid [n][ldl] (padding columns: 0), d_zerodiv [n_loci] = 1 where the
+ * reference would raise ZeroDivisionError for that locus (device memory; a
+ * flagged locus' outputs are not to be used), d_missed [u][ldl] (may be NULL)
+ * = 1 where a neighbour was consulted (the row has a count, fewer than n_nbr
+ * neighbours found so far) and had no count at that locus.  Asynchronous on
+ * the context's stream. */
+int grid_dipcn_loci(grid_ctx *ctx, int64_t n, int64_t u, int64_t n_loci, int64_t ldl, const double *d_reads,
+                    const double *d_scale, const int32_t *d_nbr, const double *d_nbr_scale,
+                    const int32_t *d_nbr_cnt, int64_t ld, int64_t n_nbr, double *d_out, uint8_t *d_valid,
+                    int32_t *d_zerodiv, uint8_t *d_missed);
 
 /* ---------------------------------------------------- step 7: haploid
  * Replaces grid/utils/hi_inference.py _run_phasing :175-226 and _compute_imp
