@@ -141,6 +141,8 @@ _SIGS = {
     "grid_text_crc32": [_vp, _vp, _vp, _vp, _i64, _vp],
     "grid_md_count": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "grid_file_status": [_vp, _vp, _vp, _i64, _vp, _i64],
+    "grid_md_cover": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64),
+                      _vp, _vp, _vp, _i64, _vp],
     "grid_h2d_async": [_vp, _vp, _vp, C.c_size_t],
     "grid_d2h_async": [_vp, _vp, _vp, C.c_size_t],
     "grid_event_new": [C.POINTER(_vp)],
@@ -824,6 +826,13 @@ class MdOpts(C.Structure):
 
 
 MD_EXOTIC, MD_NOTINK, MD_LINES = 1, 2, 4
+
+
+class CoverLoci(C.Structure):
+    """include/grid_abi.h grid_cover_loci (device pointers)."""
+    _fields_ = [("n_loci", C.c_int32), ("n_chrom", C.c_int32), ("d_names", C.c_void_p), ("d_name_off", C.c_void_p),
+                ("d_first", C.c_void_p), ("d_maxlen", C.c_void_p), ("d_start", C.c_void_p), ("d_end", C.c_void_p),
+                ("d_column", C.c_void_p)]
 
 
 def gz_text_size(buf) -> tuple[int, int] | None:

@@ -22,6 +22,10 @@
 // byte, its index from a block scan of the newline counts).  A line of more
 // than MAXLINE = 256 bytes, whether or not it passes the prefix test or ends
 // in a newline, is outside the grammar (GRID_MD_EXOTIC).
+//
+// The same text also gives the region coverage of a loci table (the
+// reference's compute_region_coverage, grid/utils/mosdepth.py:264-297):
+// k_md_cover / k_cov_walk below, behind grid_md_cover.
 #include "common.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -654,6 +658,226 @@ int excl_scan(grid_ctx *ctx, const TI *in, int64_t *out, int64_t n) {
   return GRID_OK;
 }
 
+// ---- region coverage of every locus of a table (grid_md_cover) ----
+// The reference's compute_region_coverage (grid/utils/mosdepth.py:264-297) for
+// every (file, locus) of a batch in one pass over the text: per line of a file
+// whose chromosome field EQUALS the locus's chromosome and whose overlap
+// min(END, end) - max(START, start) is > 0,
+//   region_cov = region_cov + fl(fl(q / 100) * (double)overlap)   (fp64, one
+//                multiply and one add, -ffp-contract=off, q / 100 by div100_exact)
+//   covered_bp = covered_bp + overlap                              (int64)
+// in increasing line number, then coverage = rint(100 * (region_cov /
+// covered_bp)) (IEEE /, *, round half to even: Python's round(float)), 0 when
+// covered_bp is 0.
+//
+// The reference parses all four fields of EVERY line before it looks at the
+// chromosome, so every line of the file must be in md_line's grammar (no prefix
+// test): a line outside it, an empty line, a line of more than MAXLINE bytes
+// sets GRID_MD_EXOTIC for that file alone (k_md_count has flagged bytes >= 0x80).
+// Bound of the overlap arithmetic: the grammar's START and END have at most 18
+// digits, so 0 <= START, END < 10^18 < 2^60, and the table's starts and ends
+// are required in [0, 2^60): every min, max and difference is exact in int64
+// and |overlap| < 2^60; (double)overlap is the correctly rounded conversion
+// Python's float * int makes.  covered_bp is kept below 2^62: a sum that would
+// pass it flags the file (GRID_MD_EXOTIC) instead of wrapping.
+//
+// k_md_cover is k_md_parse's geometry (the chunk in padded LDS, a 64-byte
+// segment per thread, line numbers from cline0 + the block scan), restated
+// here rather than shared: with the chunk load and the segment walk factored
+// into functions both kernels call, k_md_parse no longer compiled to the
+// parent's instructions (other register allocation, ~20 instructions fewer or
+// more per mode), and the step-4 parse is the measured one.
+// Nearly every line hits no locus: its chromosome is looked up in the table's
+// distinct names (sorted by length, then bytes), then ONE lower bound of the
+// line's END in that chromosome's loci (sorted by start) and a walk down while
+// start > START - maxlen (maxlen: the chromosome's longest locus; a locus that
+// starts at or before START - maxlen ends at or before START).  A hit appends
+// (segment = file * n_loci + locus, line, overlap, q) through an atomic cursor;
+// the hits are then sorted by (segment, line) and one lane per segment sums
+// them in line order, so nothing depends on the order the atomics arrived in.
+struct CovLoci {
+  int nchrom, nloci;
+  const char *names;          // distinct chromosome names, sorted by (length, bytes)
+  const int32_t *name_off;    // [nchrom + 1]
+  const int32_t *lfirst;      // [nchrom + 1]: loci of chromosome c, sorted by start
+  const int64_t *maxlen;      // [nchrom]
+  const int64_t *ls, *le;     // [nloci] in table order
+  const int32_t *lid;         // [nloci] the output column
+};
+constexpr int64_t COV_MAXBP = 1ll << 62, COV_MAXLINE = 0xffffffffll;
+
+__global__ __launch_bounds__(PTH) __attribute__((amdgpu_waves_per_eu(GRID_MDPARSE_WPE))) void k_md_cover(
+    const uint8_t *__restrict__ text, const int64_t *__restrict__ toff, const int64_t *__restrict__ tlen,
+    const int32_t *__restrict__ cfile, const int64_t *__restrict__ cstart, const int64_t *__restrict__ cline0,
+    CovLoci T, int32_t *__restrict__ flags, const int32_t *__restrict__ fst, unsigned long long *__restrict__ cursor,
+    unsigned long long cap, uint64_t *__restrict__ hkey, int64_t *__restrict__ hov, int32_t *__restrict__ hq) {
+  constexpr int HALO = 16, SPAN = HALO + CH + MAXLINE + 16;
+  __shared__ __attribute__((aligned(16))) uint8_t s_t[SPAN + 4 * (SPAN / 64 + 2)];
+  __shared__ int s_wsum[PTH / 64];
+  const int c = blockIdx.x, f = cfile[c], tid = threadIdx.x;
+  if (fst && fst[f]) return;
+  const int64_t L = tlen[f], a = cstart[c], b = min(L, a + CH);
+  const uint8_t *t = text + toff[f];
+  {
+    const int64_t lo = a - HALO, hi = min(L, b + MAXLINE);
+    constexpr int NW = SPAN / 16, G = GRID_MDPARSE_G;
+    for (int k0 = 0; k0 * PTH < NW; k0 += G) {
+      uint4 v[G];
+#pragma unroll
+      for (int k = 0; k < G; k++) {
+        const int w = tid + (k0 + k) * PTH;
+        const int64_t p = lo + 16 * (int64_t)w;
+        v[k] = make_uint4(0, 0, 0, 0);
+        if (w < NW && p >= 0 && p + 16 <= hi) v[k] = *reinterpret_cast<const uint4 *>(t + p);
+      }
+#pragma unroll
+      for (int k = 0; k < G; k++) {
+        const int w = tid + (k0 + k) * PTH;
+        const int64_t p = lo + 16 * (int64_t)w;
+        if (w >= NW) continue;
+        if (p >= 0 && p + 16 > hi && p < hi) {
+          uint8_t q[16];
+          for (int j = 0; j < 16; j++) q[j] = p + j < hi ? t[p + j] : 0;
+          v[k] = *reinterpret_cast<const uint4 *>(q);
+        }
+        uint32_t *d = reinterpret_cast<uint32_t *>(s_t + md_phys(16 * w));
+        d[0] = v[k].x;
+        d[1] = v[k].y;
+        d[2] = v[k].z;
+        d[3] = v[k].w;
+      }
+    }
+  }
+  __syncthreads();
+  const int64_t s0 = a + (int64_t)tid * SEG, s1 = min(b, s0 + SEG);
+  const int nw = s1 > s0 ? (int)((s1 - s0 + 15) / 16) : 0;
+  const uint32_t *seg = reinterpret_cast<const uint32_t *>(s_t + md_phys(HALO + tid * SEG));
+  auto mask = [&](int k) {
+    uint32_t mk = nl_mask16(make_uint4(seg[4 * k], seg[4 * k + 1], seg[4 * k + 2], seg[4 * k + 3]));
+    const int64_t rest = s1 - (s0 + 16 * k);
+    if (rest < 16) mk &= (1u << rest) - 1u;
+    return mk;
+  };
+  int nl = 0;
+  for (int k = 0; k < nw; k++) nl += __builtin_popcount(mask(k));
+  int incl = nl;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int y = __shfl_up(incl, d, 64);
+    if ((tid & 63) >= d) incl += y;
+  }
+  if ((tid & 63) == 63) s_wsum[tid >> 6] = incl;
+  __syncthreads();
+  int before = incl - nl;
+  for (int w = 0; w < (tid >> 6); w++) before += s_wsum[w];
+  const int64_t idx0 = cline0[c] + before;
+  int bad = 0;
+  auto line = [&](int64_t x, int len, int64_t idx) {
+    const PadText p{s_t, (int)(HALO + (x - a))};
+    int clen;
+    int64_t s, e, q;
+    if (!md_line(p, len, clen, s, e, q)) {
+      bad |= GRID_MD_EXOTIC;
+      return;
+    }
+    int lo = 0, hi = T.nchrom, ch = -1;          // the chromosome: equal, byte for byte
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1, n0 = T.name_off[mid];
+      int cmp = clen - (T.name_off[mid + 1] - n0);
+      for (int k = 0; cmp == 0 && k < clen; k++) cmp = (int)p[k] - (int)(uint8_t)T.names[n0 + k];
+      if (cmp == 0) {
+        ch = mid;
+        break;
+      }
+      if (cmp < 0) hi = mid;
+      else lo = mid + 1;
+    }
+    if (ch < 0) return;
+    const int l0 = T.lfirst[ch];
+    int l = l0, r = T.lfirst[ch + 1];            // lower bound of END in the starts: loci before it start below END
+    while (l < r) {
+      const int m = (l + r) >> 1;
+      if (T.ls[m] < e) l = m + 1;
+      else r = m;
+    }
+    const int64_t low = s - T.maxlen[ch];
+    for (int j = l - 1; j >= l0 && T.ls[j] > low; j--) {
+      const int64_t ov = min(T.le[j], e) - max(T.ls[j], s);
+      if (ov <= 0) continue;
+      if (idx > COV_MAXLINE) {
+        bad |= GRID_MD_LINES;
+        continue;
+      }
+      const unsigned long long pos = atomicAdd(cursor, 1ull);
+      if (pos < cap) {
+        hkey[pos] = ((uint64_t)((int64_t)f * T.nloci + T.lid[j]) << 32) | (uint64_t)idx;
+        hov[pos] = ov;
+        hq[pos] = (int32_t)q;
+      }
+    }
+  };
+  if (s1 > s0) {
+    int64_t cur = (s0 == 0 || s_t[md_phys((int)(HALO + (s0 - a) - 1))] == '\n') ? s0 : -1;
+    int64_t idx = idx0;
+    for (int k = 0; k < nw; k++) {
+      uint32_t mk = mask(k);
+      while (mk) {
+        const int64_t y = s0 + 16 * k + __builtin_ctz(mk);
+        mk &= mk - 1;
+        if (cur >= 0) {
+          const int64_t len = y - cur;
+          if (len > MAXLINE) bad |= GRID_MD_EXOTIC;
+          else line(cur, (int)len, idx);
+        }
+        idx++;
+        cur = y + 1 < s1 ? y + 1 : -1;
+      }
+    }
+    if (cur >= 0) {
+      const PadText p{s_t, (int)(HALO + (cur - a))};
+      const int64_t lim = min(L, cur + MAXLINE + 1) - cur;
+      int len = 0;
+      while (len < lim && p[len] != '\n') len++;
+      if (len > MAXLINE) bad |= GRID_MD_EXOTIC;
+      else line(cur, len, idx);
+    }
+  }
+  if (bad) atomicOr(flags + f, bad);
+}
+
+__global__ void k_cov_iota(uint32_t *__restrict__ p, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = (uint32_t)i;
+}
+
+// sorted hits: the lane at the head of a (file, locus) segment sums it in line order
+__global__ __launch_bounds__(256) void k_cov_walk(const uint64_t *__restrict__ key, const uint32_t *__restrict__ perm,
+                                                  int64_t n, const int64_t *__restrict__ hov,
+                                                  const int32_t *__restrict__ hq, int64_t nloci, int64_t ld,
+                                                  double *__restrict__ cov, int64_t *__restrict__ bp,
+                                                  int64_t *__restrict__ out, int32_t *__restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t sg = key[i] >> 32;
+  if (i > 0 && (key[i - 1] >> 32) == sg) return;
+  double acc = 0.0;
+  int64_t b = 0;
+  bool over = false;
+  for (int64_t j = i; j < n && (key[j] >> 32) == sg; j++) {
+    const uint32_t r = perm[j];
+    const int64_t ov = hov[r];
+    const double d = div100_exact(hq[r]) * (double)ov;
+    acc = acc + d;
+    if (b > COV_MAXBP - ov) over = true;
+    else b += ov;
+  }
+  const int64_t f = (int64_t)sg / nloci, l = (int64_t)sg % nloci;
+  cov[f * ld + l] = acc;
+  bp[f * ld + l] = b;
+  out[f * ld + l] = b > 0 ? (int64_t)rint(100.0 * (acc / (double)b)) : 0;
+  if (over) atomicOr(flags + f, GRID_MD_EXOTIC);
+}
+
 MdOpts to_opts(const grid_md_opts *h) {
   MdOpts o;
   o.prefix = h->d_prefix;
@@ -831,6 +1055,80 @@ int grid_md_parse_map(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_tof
                      (const Key2 *)d_K, nK, d_kidx, ref_nlines, d_Q, ldq, d_qrow, (unsigned long long *)d_kept,
                      d_fstatus);
   LAUNCHCHK();
+  return GRID_OK;
+}
+
+int grid_md_cover(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                  int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart, const int64_t *d_cline0,
+                  const int32_t *d_fstatus, int64_t nfiles, const grid_cover_loci *loci, uint64_t *d_hit_key,
+                  int64_t *d_hit_overlap, int32_t *d_hit_q, int64_t hit_cap, int64_t *h_nhits, double *d_region_cov,
+                  int64_t *d_covered_bp, int64_t *d_coverage, int64_t ld, int32_t *d_flags) {
+  REQUIRE(ctx && loci && h_nhits && nchunks >= 0 && nchunks <= 0x7fffffff && nfiles >= 0, "bad args");
+  REQUIRE(loci->n_loci >= 1 && loci->n_chrom >= 1 && loci->n_chrom <= loci->n_loci && ld >= loci->n_loci,
+          "bad loci table (%d loci, %d chromosomes, ld %lld)", (int)loci->n_loci, (int)loci->n_chrom, (long long)ld);
+  REQUIRE(nfiles * (int64_t)loci->n_loci < (1ll << 31), "too many (file, locus) cells for one batch");
+  REQUIRE(hit_cap >= 0 && hit_cap < (1ll << 31) && (!hit_cap || (d_hit_key && d_hit_overlap && d_hit_q)),
+          "bad hit buffer");
+  *h_nhits = 0;
+  if (nfiles == 0) return GRID_OK;
+  REQUIRE(d_region_cov && d_covered_bp && d_coverage && d_flags, "bad args");
+  void *s = nullptr;
+  int rc = grid_scratch(ctx, 256, &s);
+  if (rc) return rc;
+  unsigned long long *cursor = (unsigned long long *)s, n = 0;
+  if (nchunks > 0) {
+    HIPCHK(hipMemsetAsync(cursor, 0, 8, ctx->stream));
+    CovLoci T;
+    T.nchrom = loci->n_chrom;
+    T.nloci = loci->n_loci;
+    T.names = loci->d_names;
+    T.name_off = loci->d_name_off;
+    T.lfirst = loci->d_first;
+    T.maxlen = loci->d_maxlen;
+    T.ls = loci->d_start;
+    T.le = loci->d_end;
+    T.lid = loci->d_column;
+    hipLaunchKernelGGL(k_md_cover, dim3((unsigned)nchunks), dim3(PTH), 0, ctx->stream, d_text, d_toff, d_tlen, d_cfile,
+                       d_cstart, d_cline0, T, d_flags, d_fstatus, cursor, (unsigned long long)hit_cap, d_hit_key,
+                       d_hit_overlap, d_hit_q);
+    LAUNCHCHK();
+    HIPCHK(hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  *h_nhits = (int64_t)n;
+  if ((int64_t)n > hit_cap) return GRID_OK;        // the buffer is too small: nothing computed
+  const size_t cells = (size_t)nfiles * (size_t)ld;
+  HIPCHK(hipMemsetAsync(d_region_cov, 0, cells * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(d_covered_bp, 0, cells * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(d_coverage, 0, cells * 8, ctx->stream));
+  if (n == 0) return GRID_OK;
+  // order by (file, locus, line): one key, unique per hit (a line hits a locus once)
+  const size_t n8 = ((size_t)n * 8 + 255) & ~size_t(255), n4 = ((size_t)n * 4 + 255) & ~size_t(255);
+  // a plain allocation, not the stream-ordered pool: with hipMallocAsync a second batch of
+  // fewer hits read the previous batch's bytes at the sorted values' address
+  char *blk = nullptr;
+  HIPCHK(hipMalloc((void **)&blk, n8 + 2 * n4));
+  struct Free {
+    void *p;
+    ~Free() { (void)hipFree(p); }
+  } guard{blk};
+  uint64_t *skey = (uint64_t *)blk;
+  uint32_t *iota = (uint32_t *)(blk + n8), *perm = (uint32_t *)(blk + n8 + n4);
+  const unsigned gn = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_cov_iota, dim3(gn), dim3(256), 0, ctx->stream, iota, (int64_t)n);
+  LAUNCHCHK();
+  size_t tmp = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t *)d_hit_key, skey, (const uint32_t *)iota,
+                                            perm, (int)n, 0, 64, ctx->stream));
+  rc = grid_scratch(ctx, tmp + 256, &s);
+  if (rc) return rc;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(s, tmp, (const uint64_t *)d_hit_key, skey, (const uint32_t *)iota, perm,
+                                            (int)n, 0, 64, ctx->stream));
+  hipLaunchKernelGGL(k_cov_walk, dim3(gn), dim3(256), 0, ctx->stream, (const uint64_t *)skey, (const uint32_t *)perm,
+                     (int64_t)n, (const int64_t *)d_hit_overlap, (const int32_t *)d_hit_q, (int64_t)loci->n_loci, ld,
+                     d_region_cov, d_covered_bp, d_coverage, d_flags);
+  LAUNCHCHK();
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return GRID_OK;
 }
 

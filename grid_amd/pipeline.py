@@ -3,7 +3,11 @@
 Same YAML, same step gates, same catch-and-log-and-continue behaviour per
 step.  Steps 4-7 run on the MI355X path; steps 1-3 (CRAM indexing, read
 counting, mosdepth) are producers outside this build's scope: when enabled
-they are reported, and their output files must already exist.
+they are reported, and their output files must already exist.  One half of
+step 3 needs no CRAM and runs here behind its own key, ``mosdepth.coverage.run``:
+the coverage of a region -- or of every region of a loci table -- from the
+samples' existing regions.bed.gz files (utils/mosdepth.py), which is the counts
+file step 6 reads.
 """
 from __future__ import annotations
 
@@ -51,6 +55,15 @@ def _run(console, config):
         _oos(console, "Read counting (step 2)")
     if cfg["mosdepth"].get("run") == True:  # noqa: E712
         _oos(console, "mosdepth (step 3)")
+
+    # region coverage from the samples' existing regions.bed.gz files (the half
+    # of the reference's step 3 that needs no CRAM): the counts step 6 reads
+    if (cfg["mosdepth"].get("coverage") or {}).get("run") == True:  # noqa: E712
+        try:
+            from .utils.mosdepth import compute_region_coverages
+            compute_region_coverages(cfg, console)
+        except Exception as e:
+            log(console, f"Failed to compute region coverage: {e}", style="danger")
 
     if cfg["mosdepth"]["normalize"].get("run") == True:  # noqa: E712
         try:

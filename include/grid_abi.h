@@ -721,6 +721,41 @@ int grid_md_parse_map_general(grid_ctx *ctx, const uint8_t *d_text, const int64_
                               const int64_t *d_cline0, const grid_md_opts *opts, int32_t *d_flags, const void *d_K,
                               int64_t nK, const int32_t *d_kidx, int64_t ref_nlines, int32_t *d_Q, int64_t ldq,
                               const int32_t *d_qrow, uint64_t *d_kept, const int32_t *d_fstatus);
+/* ---- region coverage of a loci table from the same text (reference grid/utils/mosdepth.py
+ * compute_region_coverage :264-297, for every (file, locus) of the batch in one pass).
+ * The table, uploaded once: the distinct chromosome names sorted by (length, bytes); per
+ * chromosome its loci d_first[c] .. d_first[c+1]-1, sorted by start, and the length of its
+ * longest locus (max(end - start, 0)); per locus start, end (both in [0, 2^60)) and the output
+ * column d_column (a permutation of 0 .. n_loci-1).  Loci may overlap, nest or coincide. */
+typedef struct grid_cover_loci {
+  int32_t n_loci, n_chrom;         /* n_loci >= 1 */
+  const char *d_names;
+  const int32_t *d_name_off;       /* [n_chrom + 1] */
+  const int32_t *d_first;          /* [n_chrom + 1] */
+  const int64_t *d_maxlen;         /* [n_chrom] */
+  const int64_t *d_start, *d_end;  /* [n_loci] */
+  const int32_t *d_column;         /* [n_loci] */
+} grid_cover_loci;
+/* Text, chunks and d_cline0 as grid_md_count leaves them; d_fstatus as grid_file_status (may be
+ * NULL).  A line counts for a locus iff its chromosome field equals the locus's byte for byte
+ * and overlap = min(END, end) - max(START, start) > 0.  Per (file, locus), lines in increasing
+ * line number: d_region_cov += fl(fl(q / 100) * (double)overlap) in fp64 (one multiply, one
+ * add), d_covered_bp += overlap (int64); d_coverage = covered_bp > 0 ? (int64)rint(100.0 *
+ * (region_cov / (double)covered_bp)) : 0 (IEEE, round half to even).  All three are row-major
+ * [nfiles][ld], written in full.  Every line of a file must be in the canonical grammar (no
+ * prefix test): d_flags[f] |= GRID_MD_EXOTIC for a line outside it, an empty line or a line
+ * of more than 256 bytes, or a covered_bp that would reach 2^62; |= GRID_MD_LINES for a hit
+ * past line 2^32 - 1.  The rows of a flagged file mean nothing (the caller recomputes it on
+ * the host); the other files' rows stand.  Hits pass through the caller's buffer of hit_cap
+ * records (d_hit_key / d_hit_overlap / d_hit_q) and are summed in (file, locus, line) order,
+ * whatever order they arrived in.  *h_nhits = the hits of the batch: when it exceeds hit_cap
+ * NO output is written -- repeat the call with a buffer of at least *h_nhits records.
+ * Synchronises the stream. */
+int grid_md_cover(grid_ctx *ctx, const uint8_t *d_text, const int64_t *d_toff, const int64_t *d_tlen,
+                  int64_t nchunks, const int32_t *d_cfile, const int64_t *d_cstart, const int64_t *d_cline0,
+                  const int32_t *d_fstatus, int64_t nfiles, const grid_cover_loci *loci, uint64_t *d_hit_key,
+                  int64_t *d_hit_overlap, int32_t *d_hit_q, int64_t hit_cap, int64_t *h_nhits, double *d_region_cov,
+                  int64_t *d_covered_bp, int64_t *d_coverage, int64_t ld, int32_t *d_flags);
 /* d_fstatus (may be NULL in grid_md_count / grid_md_parse_map: every file parsed) = per batch
  * file, nonzero when any of its inflate units failed (the file is dropped, as the reference
  * drops a sample whose gzip does not read): grid_file_status folds the units' statuses of a
