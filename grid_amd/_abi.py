@@ -393,6 +393,11 @@ class Device:
                 b.free()
         return freed
 
+    def cached_nbytes(self, name):
+        """The size of the buffer cached under ``name`` (0: none)."""
+        b = self.__dict__.get("_cache", {}).get(name)
+        return b.nbytes if b is not None else 0
+
     def cached_bytes(self):
         return sum(b.nbytes for b in self.__dict__.get("_cache", {}).values() if b is not None)
 

@@ -19,11 +19,11 @@ def release_ingest_buffers(*devs):
     """Free what the device ingest keeps between its batches and ingests: the
     device input / text buffers cached on the step contexts (get_device) and
     on ``devs`` (Device.cached, names "ingest_*"), and the host staging
-    (ingest_device._STAGING).  Returns (device bytes, host bytes) released."""
-    from .utils import ingest_device
+    (gz_batch._STAGING).  Returns (device bytes, host bytes) released."""
+    from .utils import gz_batch
     ds = {id(d): d for d in list(_dev.values()) + list(devs) if getattr(d, "ctx", None)}
     dbytes = sum(d.release_cached("ingest_") for d in ds.values())
-    return dbytes, ingest_device.release_staging()
+    return dbytes, gz_batch.release_staging()
 
 
 def step4_done(dev=None):

@@ -40,7 +40,8 @@ import numpy as np
 
 from .. import _abi
 from .._abi import call
-from .ingest_device import READ_THREADS, _align, _chunks, _gpu_inflate
+from .gz_batch import READ_THREADS, align, chunk_table, fold_members, member_units, whole_units
+from .gz_batch import gpu_inflate as _gpu_inflate      # cover_files launches through this module's name (a test seam)
 from .mosdepth import region_sums, coverage_value
 
 BATCH_FILES = 256               # files per batch (n_loci * files stays far below 2^31)
@@ -185,7 +186,7 @@ def cover_files(dev, paths, loci, batch_files=None, hit_capacity=None, batch_tex
             while queue and len(fs) < batch_files:
                 f, fut = queue[0]
                 one = fut.result()
-                size += _align(max(min(one[1][0], 1032 * one[0].size + 1024) if one[1] else 0, 1))
+                size += align(max(min(one[1][0], 1032 * one[0].size + 1024) if one[1] else 0, 1))
                 if fs and size > batch_text:
                     break
                 queue.popleft()
@@ -202,8 +203,8 @@ def cover_files(dev, paths, loci, batch_files=None, hit_capacity=None, batch_tex
             # a damaged trailer must not size the buffers
             tsize = np.array([min(ts[0], 1032 * v.size + 1024) if ts else 0 for v, ts, _ in info], np.int64)
             off = np.zeros(nb + 1, np.int64)
-            off[1:] = np.cumsum([_align(max(v.size, 1)) for v, _, _ in info])
-            tcap = np.array([_align(max(c, 1)) for c in tsize], np.int64)
+            off[1:] = np.cumsum([align(max(v.size, 1)) for v, _, _ in info])
+            tcap = np.array([align(max(c, 1)) for c in tsize], np.int64)
             toff = np.zeros(nb + 1, np.int64)
             toff[1:] = np.cumsum(tcap)
             # the batch's device buffers are kept between batches (an allocation of GBs per batch
@@ -221,29 +222,15 @@ def cover_files(dev, paths, loci, batch_files=None, hit_capacity=None, batch_tex
                 if info[k][0].size and not info[k][1]:
                     gst[k] = _abi.GZ_EHEADER                  # not gzip
             if wu:                                            # plain gzip: one wave per file
-                mcap = max(1, int(max(info[k][0].size // 4096 + 16 for k in wu)))
-                units = ([off[k] for k in wu], [info[k][0].size for k in wu], [toff[k] for k in wu],
-                         [tsize[k] for k in wu])
+                units, mcap = whole_units(off, [v.size for v, _, _ in info], toff, tsize, wu)
                 whole = _gpu_inflate(dev, d_in, d_text, units, mcap)
                 gst[wu], tlen[wu] = whole[2].numpy(), whole[3].numpy()
             if mu:                                            # BGZF: one wave per member
-                uo, ul, to, tc, owner = [], [], [], [], []
-                for k in mu:
-                    ms, ml, mi = info[k][2]
-                    cum = np.zeros(len(mi), np.int64)
-                    np.cumsum(mi[:-1], out=cum[1:])
-                    uo.append(off[k] + ms)
-                    ul.append(ml)
-                    to.append(toff[k] + cum)
-                    tc.append(mi.astype(np.int64))
-                    owner.append(np.full(len(mi), k, np.int64))
-                units = [np.concatenate(x) for x in (uo, ul, to, tc)]
-                owner = np.concatenate(owner)
+                *units, owner = member_units([m for _, _, m in info], off, toff, mu)
                 parts = _gpu_inflate(dev, d_in, d_text, units, 1)
                 d_owner, d_bad = dev.upload(owner), dev.alloc(nb, np.int32)
                 call("grid_file_status", dev.ctx, parts[2].ptr, d_owner.ptr, len(owner), d_bad.ptr, nb)
-                tot = np.zeros(nb, np.int64)
-                np.add.at(tot, owner, parts[3].numpy())
+                tot = fold_members(nb, owner, unit_len=parts[3].numpy())[1]
                 gst[mu], tlen[mu] = d_bad.numpy()[mu], tot[mu]
             for k in range(nb):
                 f = fs[k]
@@ -271,7 +258,7 @@ def cover_files(dev, paths, loci, batch_files=None, hit_capacity=None, batch_tex
             cov = np.zeros((nb, ld), np.float64)
             bp = np.zeros((nb, ld), np.int64)
             out = np.zeros((nb, ld), np.int64)
-            cfile, cstart, cfirst, nch = _chunks(okb, tlen)
+            cfile, cstart, cfirst, nch = chunk_table(okb, tlen)
             if nch:
                 fst = np.ones(nb, np.int32)
                 fst[okb] = 0

@@ -58,6 +58,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 import time
 from collections.abc import Sequence
 from concurrent.futures import ThreadPoolExecutor
@@ -66,8 +67,11 @@ import numpy as np
 
 from .. import _abi
 from .._abi import MdOpts, call
+# the batch layer shared with the coverage and step 5's read; device.py, tools and tests reach some through here
+from .gz_batch import (CH, READ_THREADS, _STAGING, align, chunk_table, fold_members, gpu_inflate,  # noqa: F401
+                       member_units, release_staging, staging, staging_bytes, whole_units)
+_chunks, _staging = chunk_table, staging    # their names before gz_batch
 
-CH = 16384                      # parse chunk (mosdepth_dev.hip CH)
 BATCH_IN = 4 << 30              # compressed bytes per batch
 BATCH_TEXT = 24 << 30           # inflated bytes per batch
 FIRST_BATCH_IN = 256 << 20      # the first batch (read and inflated synchronously: the reference key list)
@@ -93,8 +97,6 @@ HOST_FRAC = float(os.environ.get("GRID_INGEST_HOST_FRAC", "0.25"))
 HOST_RATE_PER_THREAD = 0.77e9
 GPU_INFLATE_RATE = 63e9          # r05ag: BGZF members (tools/bench_inflate.py --bgzf --units)
 HOST_FRAC_MIN = 0.2
-# file reads and member tables: a pool of their own, independent of `threads`
-READ_THREADS = int(os.environ.get("GRID_INGEST_READ_THREADS", "8"))
 
 
 def host_frac(threads):
@@ -117,6 +119,12 @@ class DeviceIngestKeys(DeviceIngestUnsupported):
 KEY_MODES = ("strict", "general")
 
 
+def _trace(fmt, *args):
+    """Phase times on stderr (GRID_INGEST_TRACE)."""
+    if TRACE:
+        print("[ingest] " + fmt.format(*args), file=sys.stderr, flush=True)
+
+
 def _flag_reason(flags):
     """Why a file's parse flags hand the cohort over."""
     if flags & _abi.MD_EXOTIC:
@@ -124,73 +132,6 @@ def _flag_reason(flags):
     if flags & _abi.MD_NOTINK:
         return "a key outside K"
     return "more than 2^31 - 3 lines (general keys)"
-
-
-def _align(x, a=256):
-    return -(-int(x) // a) * a
-
-
-class _Pinned:
-    """Reusable host staging.  Page-locked (grid_host_alloc: no torch in the
-    step path -- a first ``import torch`` costs seconds on a fresh host) for
-    the asynchronous copies of host-inflated text; PAGEABLE (``pinned=False``)
-    for the compressed input: the runtime copies pageable memory to HBM as fast
-    as page-locked here (56 vs 52-58 GB/s, profiles/r04i_host_read_h2d.jsonl),
-    while page-locking 4 GB costs ~0.65 s that stalls every other HIP call."""
-
-    def __init__(self, bound, pinned=True):
-        self.b = None
-        self.bound = int(bound)        # the size a request normally stays within
-        self.pinned = pinned
-
-    def get(self, n):
-        if self.b is None or self.b.nbytes < n:
-            if self.b is not None:
-                self.b.free()
-            # room to grow at once: a buffer re-pinned a few MB larger each
-            # batch stalled that batch's copy to HBM by ~1 s (profiles/r03q)
-            nb = max(int(n), min(2 * int(n), self.bound), 1)
-            self.b = _abi.PinnedBuf(nb) if self.pinned else _Pageable(nb)
-        return self.b.array
-
-
-_libc = C.CDLL(None, use_errno=True)
-_libc.mmap.restype = C.c_void_p
-_libc.mmap.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]
-_libc.munmap.argtypes = [C.c_void_p, C.c_size_t]
-_libc.madvise.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-
-
-class _Pageable:
-    """Pageable staging mapped through libc (anonymous, transparent huge pages
-    advised, as NumPy does for large arrays) and unmapped through a foreign
-    call, so the multi-GB munmap runs without the GIL (a NumPy array's free
-    holds it: the staging released on a background thread stalled the step's
-    own thread for ~0.5 s at the end of the config-2 ingest)."""
-
-    def __init__(self, nbytes):
-        self.nbytes = max(int(nbytes), 1)
-        p = _libc.mmap(None, self.nbytes, 3, 0x22, -1, 0)      # PROT_READ|WRITE, MAP_PRIVATE|ANONYMOUS
-        if p is None or p == C.c_void_p(-1).value:
-            raise MemoryError(f"staging of {self.nbytes} bytes")
-        _libc.madvise(p, self.nbytes, 14)                      # MADV_HUGEPAGE (advice only)
-        self.ptr = p
-        self.array = np.ctypeslib.as_array((C.c_uint8 * self.nbytes).from_address(self.ptr))
-        # its own reference: at interpreter exit the module's globals may be
-        # gone before this object's __del__ runs
-        self._munmap = _libc.munmap
-
-    def free(self):
-        if self.ptr:
-            self.array = None
-            self._munmap(self.ptr, self.nbytes)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def _opts(dev, prefix, window, excluded, keep):
@@ -265,66 +206,6 @@ class _Split:
             self.cpu = (1 - a) * self.cpu + a * c_bytes / (t_cpu * self.threads)
 
 
-def _gpu_inflate(dev, d_in, d_text, units, mcap):
-    """Launch grid_gunzip_batch over units (in_off, in_len, out_off, cap);
-    returns the device buffers to read after the stream syncs."""
-    n = len(units[0])
-    d = [dev.upload(np.asarray(u, np.int64)) for u in units]
-    mem = dev.alloc(n * mcap * _abi.GZ_MEMBER_BYTES, np.uint8)
-    st, ln, nm = dev.alloc(n, np.int32), dev.alloc(n, np.int64), dev.alloc(n, np.int32)
-    call("grid_gunzip_batch", dev.ctx, d_in.ptr, d[0].ptr, d[1].ptr, n, d_text.ptr, d[2].ptr, d[3].ptr, mem.ptr,
-         mcap, st.ptr, ln.ptr, nm.ptr)
-    return d, mem, st, ln, nm
-
-
-def _chunks(files, tlen):
-    """Chunk table of the files (batch-local indices) with text: per chunk its
-    file and start; per file its first chunk (cfirst[k], k in file order)."""
-    files = np.asarray(files, np.int64)
-    n = -(-np.asarray(tlen, np.int64)[files] // CH) if len(files) else np.zeros(0, np.int64)
-    cfirst = np.zeros(len(files) + 1, np.int32)
-    np.cumsum(n, out=cfirst[1:])
-    tot = int(cfirst[-1])
-    if tot == 0:
-        return np.zeros(1, np.int32), np.zeros(1, np.int64), cfirst, 0
-    cfile = np.repeat(files, n).astype(np.int32)
-    cstart = (np.arange(tot, dtype=np.int64) - np.repeat(cfirst[:-1].astype(np.int64), n)) * CH
-    return cfile, cstart, cfirst, tot
-
-
-# The host staging of the device ingest, kept between the batches and the
-# ingests of one run: releasing tens of GB of staging the HIP runtime has
-# copied from (page-locked, or pageable pages it has seen) holds the runtime for
-# 0.4-0.8 s, and every HIP call of the step after the ingest waited for it (r04y,
-# r04ac).  release_staging() frees it: at the end of a pipeline run or of a
-# standalone step 4, and when the ingest hands over to the host parser
-# (grid_amd/device.py release_ingest_buffers).
-_STAGING = {}
-
-
-def _staging(name, bound, pinned=False):
-    b = _STAGING.get(name)
-    if b is None:
-        b = _STAGING[name] = _Pinned(bound, pinned=pinned)
-    return b
-
-
-def staging_bytes():
-    return sum(p.b.nbytes for p in _STAGING.values() if p.b is not None)
-
-
-def release_staging():
-    """Free the kept host staging; returns the bytes released."""
-    freed = 0
-    for p in list(_STAGING.values()):
-        if p.b is not None:
-            freed += p.b.nbytes
-            p.b.free()
-            p.b = None
-    _STAGING.clear()
-    return freed
-
-
 class _Async:
     """The device ingest's pipelined batches (every file BGZF, all inflated by
     the GPU; after the first batch, which builds the key list K synchronously).
@@ -351,21 +232,13 @@ class _Async:
         self.h2d = [_abi.Event(), _abi.Event()]
         self.done = [_abi.Event(), _abi.Event()]
         self.issued = [False, False]
-        self.arena_h = [_staging("arena0", 64 << 20), _staging("arena1", 64 << 20)]
+        self.arena_h = [staging("arena0", 64 << 20), staging("arena1", 64 << 20)]
         self.arena_d = [None, None]
         self.scr = [None, None]                 # per parity: member table, chunk counts/lines, file status
         self.out = []                           # per batch: (fs, owner, unit status, unit length, flags, kept, okb)
         self.htext = [_abi.Event(), _abi.Event()]   # host-inflated text of parity p is in HBM
         self.hbad = []                          # host-share files whose text failed its CRC in HBM
         self.one = None                         # page-locked int32 1: a failed host-share file's device status
-
-    @staticmethod
-    def _pack(parts):
-        offs, pos = [], 0
-        for a in parts:
-            offs.append(pos)
-            pos += _align(a.nbytes)
-        return offs, pos
 
     def batch(self, bi, fs, buf, off, caps_, gz, members, toff, d_in, d_text, fsizes, hshare=None):
         """hshare: (files, future) -- files of the batch the host threads inflate
@@ -377,28 +250,16 @@ class _Async:
         nb = len(fs)
         mu = [k for k in range(nb) if gz[k] and fsizes[k] > 0 and members[k] is not None]
         hset = set(hshare[0]) if hshare else set()
-        uo, ul, to, tc, owner = [], [], [], [], []
-        for k in mu:
-            if k in hset:
-                continue
-            ms, ml, mi = members[k]
-            uo.append(off[k] + ms)
-            ul.append(ml)
-            cum = np.zeros(len(mi), np.int64)
-            np.cumsum(mi[:-1], out=cum[1:])
-            to.append(toff[k] + cum)
-            tc.append(mi.astype(np.int64))
-            owner.append(np.full(len(mi), k, np.int64))
-        cat = (lambda x: np.concatenate(x) if x else np.zeros(0, np.int64))
-        units = [cat(x) for x in (uo, ul, to, tc, owner)]
+        units = list(member_units(members, off, toff, [k for k in mu if k not in hset]))
         nu = len(units[0])
         tlen = np.zeros(nb, np.int64)               # text of a file that inflates: its members' ISIZEs
         for k in mu:
             tlen[k] = int(members[k][2].astype(np.int64).sum())
         okb = [k for k in mu if tlen[k] > 0]
-        cfile, cstart, cfirst, nch = _chunks(okb, tlen)
+        cfile, cstart, cfirst, nch = chunk_table(okb, tlen)
         parts = units + [tlen, np.ascontiguousarray(toff[:nb]), np.asarray(fs, np.int32), cfile, cstart, cfirst]
-        offs, nbytes = self._pack(parts)
+        sz = align(np.array([a.nbytes for a in parts]))       # one arena, every table 256-aligned
+        offs, nbytes = (np.cumsum(sz) - sz).tolist(), int(sz.sum())
         # the arena of parity p: its previous copy (batch bi-2) must be done
         if self.issued[p]:
             self.h2d[p].host_wait()
@@ -500,9 +361,7 @@ class _Async:
             bad[hdr_bad] = _abi.GZ_EHEADER
             bad[hfail] = _abi.GZ_EDATA
             if nu:
-                st = ust.numpy()[:nu]
-                # a member past its BGZF size is corrupt (dropped), not several members
-                np.maximum.at(bad, owner, np.where(st == _abi.GZ_ESPACE, _abi.GZ_EDATA, st))
+                np.maximum(bad, fold_members(nb, owner, ust.numpy()[:nu])[0], out=bad)
             bf, bkv = bflags.numpy(), bk.numpy()
             for k in okb:
                 if bad[k] == 0 and bf[k]:
@@ -528,6 +387,227 @@ class _Async:
             self.out = []
             self.arena_d = [None, None]
             self.scr = [None, None]
+
+
+class _Host:
+    """The host side of one ingest, shared by its batches: the thread pools,
+    the staging, the copy context and the GPU/CPU split."""
+
+    def __init__(self, dev, paths, sizes, batches, threads):
+        self.dev, self.paths, self.sizes, self.batches = dev, paths, sizes, batches
+        self.pins = [staging("in0", BATCH_IN + 512), staging("in1", BATCH_IN + 512)]
+        self.first = staging("first", FIRST_BATCH_IN + 512)        # the (small) first batch: K, quickly
+        self.stages = [staging("text0", STAGE + 512, pinned=True), staging("text1", STAGE + 512, pinned=True)]
+        nthreads = max(1, min(int(threads or 1), 32))
+        self.pool = ThreadPoolExecutor(nthreads)   # host inflate (the host share, non-BGZF files)
+        self.iopool = ThreadPoolExecutor(max(1, READ_THREADS))   # file reads + member tables
+        self.rpool = ThreadPoolExecutor(1)         # the next batch's read (its files on `iopool`)
+        self.hfrac = host_frac(nthreads)
+        self.copier = ThreadPoolExecutor(1)        # H2D of CPU-inflated text, on its own stream
+        self.waiter = ThreadPoolExecutor(1)        # notes when the GPU's inflate ends
+        self.hctl = ThreadPoolExecutor(1)          # pipelined batches: the host share's inflate (its files on `pool`)
+        self.hstages = [staging("host0", 8 << 30), staging("host1", 8 << 30)]
+        self.cdev = _abi.Device(dev.index)         # its own non-blocking stream
+        self.split = _Split(nthreads)
+        self.h2d_done = [None] * len(batches)      # per pipelined batch: the event after its copies to HBM
+
+    def close(self):
+        for p in (self.rpool, self.iopool, self.pool, self.copier, self.waiter, self.hctl):
+            p.shutdown(wait=True)
+        self.cdev.close()
+
+    def read(self, bi):
+        """Batch bi's files read into staging: (the buffer, the files' offsets in
+        it, per file (text size, members) or None, per file its BGZF members or None)."""
+        fs, sizes, paths = self.batches[bi], self.sizes, self.paths
+        off = np.zeros(len(fs) + 1, np.int64)
+        off[1:] = np.cumsum(align(np.maximum(sizes[fs], 1)))
+        if bi >= 2 and self.h2d_done[bi - 2] is not None:
+            self.h2d_done[bi - 2].host_wait()        # pins[bi % 2] still feeds batch bi-2's copy
+        buf = (self.first if bi == 0 else self.pins[bi % 2]).get(int(off[-1]) + 256)
+
+        def one(k):
+            f = fs[k]
+            with open(paths[f], "rb") as fh:
+                n = fh.readinto(memoryview(buf)[off[k]:off[k] + sizes[f]])
+            if n != sizes[f]:
+                raise DeviceIngestUnsupported(f"{paths[f]} changed while reading")
+            if not sizes[f]:
+                return (0, 0), None
+            v = buf[off[k]:off[k] + sizes[f]]
+            return _abi.gz_text_size(v), _abi.gz_members(v)
+        info = list(self.iopool.map(one, range(len(fs))))
+        return buf, off, [i[0] for i in info], [i[1] for i in info]
+
+    def share(self, bi, todo, buf, off, fs, caps_):
+        """A pipelined batch's host share as _Async.batch takes it (None: the GPU
+        inflates all): every step-th file to the host threads, which start now,
+        beside the GPU's work on the previous batch and this batch's copies."""
+        if not (self.hfrac > 0 and len(todo) > 1):
+            return None
+        step = max(2, int(round(1.0 / self.hfrac)))
+        hfiles = todo[step - 1::step]
+        so, pos = {}, 0
+        for k in hfiles:
+            so[k] = pos
+            pos += align(int(caps_[k]))
+        harr = self.hstages[bi % 2].get(pos + 256)
+
+        def one(k):
+            v = buf[off[k]:off[k] + self.sizes[fs[k]]]
+            st_, ln_, crc_ = _abi.gunzip_host(v, harr[so[k]:so[k] + int(caps_[k])], with_crc=True)
+            return k, (int(st_), int(ln_), int(crc_), harr, so[k])
+        return hfiles, self.hctl.submit(lambda: dict(self.pool.map(one, hfiles)))
+
+    def inflate(self, buf, off, fs, caps_, gz, members, toff, d_in, d_text, plan):
+        """Inflate the batch's files into d_text + toff[k], the GPU's and the
+        CPU's (``plan``) at once; (status, length) per file."""
+        dev, cdev, sizes, fsz, nb = self.dev, self.cdev, self.sizes, self.sizes[fs], len(fs)
+        # an empty file: no lines (gzip.open reads nothing); not gzip: dropped
+        gst = np.where((fsz > 0) & ~gz, _abi.GZ_EHEADER, 0).astype(np.int32)
+        tlen, hcrc = np.zeros(nb, np.int64), np.zeros(nb, np.uint32)
+        on_gpu, on_cpu = plan
+        t0 = time.perf_counter()
+        launched = []                                  # (files, each unit's file or None, gpu_inflate's buffers)
+        if on_gpu:
+            call("grid_h2d", dev.ctx, d_in.ptr, buf.ctypes.data, int(off[-1]))
+            mu = [k for k in on_gpu if members[k] is not None]
+            wu = [k for k in on_gpu if members[k] is None]
+            if wu:                                     # whole files: one wave each, started first
+                units, mcap = whole_units(off, fsz, toff, caps_, wu)
+                launched.append((wu, None, gpu_inflate(dev, d_in, d_text, units, mcap)))
+            if mu:                                     # BGZF: one wave per member
+                units = member_units(members, off, toff, mu)
+                launched.append((mu, units[4], gpu_inflate(dev, d_in, d_text, units[:4], 1)))
+            gpu_done = self.waiter.submit(lambda: (dev.sync(), time.perf_counter())[1])
+        # CPU files meanwhile: sub-batches through two pinned stages, each
+        # copied to HBM on the copy stream while the next one inflates
+        pend = [None, None]
+        c_bytes = i = sb = 0
+        while i < len(on_cpu):
+            grp, room = [], 0
+            while i < len(on_cpu) and (not grp or room + align(caps_[on_cpu[i]]) <= STAGE):
+                grp.append(on_cpu[i])
+                room += align(caps_[on_cpu[i]])
+                i += 1
+            j = sb % 2
+            sb += 1
+            if pend[j] is not None:
+                pend[j].result()
+            stage = self.stages[j].get(room + 256)
+            soff = np.zeros(len(grp) + 1, np.int64)
+            soff[1:] = np.cumsum(align(caps_[grp]))
+
+            def one(t, grp=grp, stage=stage, soff=soff):
+                k = grp[t]
+                v = buf[off[k]:off[k] + sizes[fs[k]]]
+                return _abi.gunzip_host(v, stage[soff[t]:soff[t] + caps_[k]], with_crc=True)
+            res = list(self.pool.map(one, range(len(grp))))
+            for t, k in enumerate(grp):
+                gst[k], tlen[k], hcrc[k] = res[t]
+                c_bytes += int(tlen[k])
+
+            def h2d(grp=grp, stage=stage, soff=soff, res=res):
+                for t, k in enumerate(grp):
+                    if res[t][0] == 0 and res[t][1]:
+                        call("grid_h2d", cdev.ctx, d_text.ptr + int(toff[k]), stage.ctypes.data + int(soff[t]),
+                             int(res[t][1]))
+            pend[j] = self.copier.submit(h2d)
+        t_cpu = time.perf_counter() - t0
+        for p_ in filter(None, pend):
+            p_.result()
+        if on_cpu and XSTREAM_WAIT:
+            # the parse kernels on dev's stream read text the copy stream wrote
+            # over d_text -- lines the previous batch's kernels had cached: order
+            # the stream behind the copies through the runtime (event + wait), not
+            # through the host's view of their completion alone
+            call("grid_stream_after", dev.ctx, cdev.ctx)
+        hk = [k for k in on_cpu if gst[k] == 0 and tlen[k] > 0]
+        if hk:
+            # the guard: the host-inflated text as it sits in HBM against the CRC
+            # of its gzip trailers, read on dev's stream (where the parse runs)
+            if AFTER_HOST_TEXT is not None:
+                AFTER_HOST_TEXT(dev, d_text, toff, hk)
+            got = _abi.text_crc32(dev, d_text.ptr, toff[hk], tlen[hk])
+            bad = [fs[k] for k, c in zip(hk, got) if int(c) != int(hcrc[k])]
+            if bad:
+                raise DeviceIngestUnsupported(f"{self.paths[bad[0]]}: its text in HBM does not match its gzip CRC "
+                                              f"({len(bad)} host-inflated file(s))")
+        g_mem, g_whole, t_gpu = 0, 0, 0.0
+        if launched:
+            t_gpu = gpu_done.result() - t0
+            for ks, owner, (_d, _mem, st, ln, _nm) in launched:
+                ust, uln = st.numpy(), ln.numpy()
+                if owner is None:
+                    gst[ks], tlen[ks] = ust, uln
+                    g_whole = max(g_whole, int(uln.max()))
+                else:
+                    bad, tot = fold_members(nb, owner, ust, uln)
+                    gst[ks], tlen[ks] = bad[ks], tot[ks]
+                    g_mem += int(uln.sum())
+        self.split.learn(g_mem, g_whole, t_gpu, c_bytes, t_cpu)
+        _trace("batch files gpu {} cpu {} text gpu {:.3e} cpu {:.3e} B  t_gpu {:.3f} t_cpu {:.3f} s  rates gpu {:.3e} "
+               "cpu/thread {:.3e} B/s", len(on_gpu), len(on_cpu), g_mem + g_whole, c_bytes, t_gpu, t_cpu,
+               self.split.gpu, self.split.cpu)
+        return gst, tlen
+
+
+def _reference_keys(dev, opts, general, paths, fs, okb, tlen, toff, chunks, cnl, cline0, d_text, d_toff, d_tl, bflags):
+    """(K, kidx, nK, ref_nlines) from the first batch with text.  The reference
+    file is the one with the most text (a short or truncated
+    file sorted first no longer sends the cohort to the host parser; K must hold
+    every later file's keys, which the largest file does).  ``chunks``: the
+    batch's chunk_table; cnl, cline0: grid_md_count's lines per chunk."""
+    _cfile, cstart, cfirst, _nch = chunks
+    ri = int(np.argmax(tlen[okb]))
+    r = okb[ri]
+    c0, c1 = int(cfirst[ri]), int(cfirst[ri + 1])
+    rc_file = np.zeros(c1 - c0, np.int32) + r
+    cl, nl = cline0.numpy()[c0:c1], cnl.numpy()[c0:c1]
+    tail = np.zeros(1, np.uint8)
+    call("grid_d2h", dev.ctx, tail.ctypes.data, d_text.ptr + int(toff[r] + tlen[r] - 1), 1)
+    ref_nlines = int(cl[-1] + nl[-1]) + (0 if tail[0] == 10 else 1)
+    nr = max(ref_nlines, 1)
+    kline, keys_line = dev.alloc(nr, np.uint8), dev.alloc((nr, 2), np.int64)
+    K, kidx = dev.alloc((nr, 2), np.int64), dev.alloc(nr, np.int32)
+    h_nK, h_uns = C.c_int64(), C.c_int32()
+    d_rcf, d_rcs, d_rcl = dev.upload(rc_file), dev.upload(cstart[c0:c1]), dev.upload(cl)
+    if general:
+        if ref_nlines >= 1 << 31:
+            raise DeviceIngestUnsupported(f"{paths[fs[r]]}: {_flag_reason(_abi.MD_LINES)}")
+        # K: the kept keys sorted and de-duplicated, any order, any repeats
+        call("grid_md_parse_ref_general", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
+             d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
+             kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK))
+    else:
+        call("grid_md_parse_ref", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
+             d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
+             kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK), C.byref(h_uns))
+    if h_uns.value:
+        raise DeviceIngestKeys("the reference file's keys are not strictly increasing")
+    if h_nK.value == 0:
+        raise DeviceIngestUnsupported("the reference file keeps no record")
+    return K, kidx, h_nK.value, ref_nlines
+
+
+def _finish(dev, Q, nK, K, kept, status, nfiles, min_depth, max_depth, general, t_start):
+    """grid_md_finish over the placed matrix (means, valid columns, empty-sample filter): the full result."""
+    rows = np.array([f for f in range(nfiles) if status[f] == 0], np.int32)
+    mean, valid, cpos = dev.alloc(nK, np.float64), dev.alloc(nK, np.int32), dev.alloc(nK, np.int64)
+    present, nvalid = dev.alloc(max(nfiles, 1), np.uint64), dev.alloc(max(nfiles, 1), np.uint64)
+    m = C.c_int64()
+    _trace("finish buffers at {:.3f} s", time.perf_counter() - t_start)
+    d_rows = dev.upload(rows if rows.size else np.zeros(1, np.int32))
+    call("grid_md_finish", dev.ctx, Q.ptr, nK, nK, nfiles, d_rows.ptr, len(rows), float(min_depth),
+         float(max_depth), mean.ptr, valid.ptr, cpos.ptr, present.ptr, nvalid.ptr, C.byref(m))
+    pres, nval, kh = present.numpy()[:nfiles], nvalid.numpy()[:nfiles], kept.numpy()[:nfiles]
+    if np.any(pres[rows] != kh[rows]):
+        if general:
+            # the integrity guard: every present cell was filled by exactly one line's resolve
+            raise DeviceIngestUnsupported("an unresolved cell in a file's row (general keys)")
+        raise DeviceIngestKeys("a repeated (start, end) key in a file")
+    _trace("finish done at {:.3f} s", time.perf_counter() - t_start)
+    return rows, (Q, nK, valid, cpos, K, m.value), nval, status
 
 
 def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, threads=16, ref=None,
@@ -561,176 +641,18 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
     sizes = np.array([os.path.getsize(p) if p else -1 for p in paths], np.int64)
     status = np.where(sizes < 0, 3, 0).astype(np.int32)       # 3: missing (ingest.cpp FS_MISSING)
     kept = dev.zeros(max(nfiles, 1), np.uint64)
-    order = [f for f in range(nfiles) if sizes[f] >= 0]
-    # batches in file order
-    batches, cur, cin = [], [], 0
-    for f in order:
+    batches, cur, cin = [], [], 0                              # batches in file order
+    for f in np.flatnonzero(sizes >= 0).tolist():
         lim = min(FIRST_BATCH_IN, BATCH_IN) if not batches and ref is None else BATCH_IN
-        if cur and cin + _align(sizes[f]) > lim:
+        if cur and cin + align(sizes[f]) > lim:
             batches.append(cur)
             cur, cin = [], 0
         cur.append(f)
-        cin += _align(sizes[f])
+        cin += align(sizes[f])
     if cur:
         batches.append(cur)
-    in_need = 256 + max((sum(_align(max(sizes[f], 1)) for f in b) for b in batches), default=0)
-    pins = [_staging("in0", BATCH_IN + 512), _staging("in1", BATCH_IN + 512)]
-    first = _staging("first", FIRST_BATCH_IN + 512)        # the (small) first batch: K, quickly
-    stages = [_staging("text0", STAGE + 512, pinned=True), _staging("text1", STAGE + 512, pinned=True)]
-    nthreads = max(1, min(int(threads or 1), 32))
-    pool = ThreadPoolExecutor(nthreads)   # host inflate (the host share, non-BGZF files)
-    iopool = ThreadPoolExecutor(max(1, READ_THREADS))   # file reads + member tables
-    rpool = ThreadPoolExecutor(1)         # the next batch's read (its files on `iopool`)
-    hfrac = host_frac(nthreads)
-    copier = ThreadPoolExecutor(1)        # H2D of CPU-inflated text, on its own stream
-    waiter = ThreadPoolExecutor(1)        # notes when the GPU's inflate ends
-    hctl = ThreadPoolExecutor(1)          # pipelined batches: the host share's inflate (its files on `pool`)
-    hstages = [_staging("host0", 8 << 30), _staging("host1", 8 << 30)]
-    cdev = _abi.Device(dev.index)          # its own non-blocking stream
-    split = _Split(nthreads)
-
-    h2d_done = [None] * len(batches)       # per pipelined batch: the event after its copies to HBM
-
-    def read_batch(bi):
-        fs = batches[bi]
-        off = np.zeros(len(fs) + 1, np.int64)
-        off[1:] = np.cumsum([_align(max(sizes[f], 1)) for f in fs])
-        if bi >= 2 and h2d_done[bi - 2] is not None:
-            h2d_done[bi - 2].host_wait()        # pins[bi % 2] still feeds batch bi-2's copy
-        buf = (first if bi == 0 else pins[bi % 2]).get(int(off[-1]) + 256)
-
-        def one(k):
-            f = fs[k]
-            with open(paths[f], "rb") as fh:
-                n = fh.readinto(memoryview(buf)[off[k]:off[k] + sizes[f]])
-            if n != sizes[f]:
-                raise DeviceIngestUnsupported(f"{paths[f]} changed while reading")
-            if not sizes[f]:
-                return (0, 0), None
-            v = buf[off[k]:off[k] + sizes[f]]
-            return _abi.gz_text_size(v), _abi.gz_members(v)
-        info = list(iopool.map(one, range(len(fs))))
-        return buf, off, [i[0] for i in info], [i[1] for i in info]
-
-    def inflate(buf, off, fs, caps_, gz, members, toff, d_in, d_text, plan):
-        """Inflate the batch's files into d_text + toff[k]; (status, length) per file."""
-        nb = len(fs)
-        gst = np.zeros(nb, np.int32)
-        tlen = np.zeros(nb, np.int64)
-        hcrc = np.zeros(nb, np.uint32)
-        todo = [k for k in range(nb) if gz[k] and sizes[fs[k]] > 0]
-        for k in range(nb):
-            if not sizes[fs[k]]:
-                gst[k] = 0                             # an empty file: no lines (gzip.open reads nothing)
-            elif not gz[k]:
-                gst[k] = _abi.GZ_EHEADER
-        bgzf = {k: members[k] is not None for k in todo}
-        on_gpu, on_cpu = plan
-        t0 = time.perf_counter()
-        launched = []
-        if on_gpu:
-            call("grid_h2d", dev.ctx, d_in.ptr, buf.ctypes.data, int(off[-1]))
-            mu = [k for k in on_gpu if bgzf[k]]
-            wu = [k for k in on_gpu if not bgzf[k]]
-            if wu:                                     # whole files: one wave each, started first
-                mcap = max(1, int(max(sizes[fs[k]] // 4096 + 16 for k in wu)))
-                units = ([off[k] for k in wu], [sizes[fs[k]] for k in wu], [toff[k] for k in wu],
-                         [caps_[k] for k in wu])
-                launched.append(("whole", wu, None, _gpu_inflate(dev, d_in, d_text, units, mcap)))
-            if mu:                                     # BGZF: one wave per member
-                uo, ul, to, tc, owner = [], [], [], [], []
-                for k in mu:
-                    ms, ml, mi = members[k]
-                    uo.append(off[k] + ms)
-                    ul.append(ml)
-                    cum = np.zeros(len(mi), np.int64)
-                    np.cumsum(mi[:-1], out=cum[1:])
-                    to.append(toff[k] + cum)
-                    tc.append(mi.astype(np.int64))
-                    owner.append(np.full(len(mi), k, np.int64))
-                units = [np.concatenate(x) for x in (uo, ul, to, tc)]
-                launched.append(("members", mu, np.concatenate(owner), _gpu_inflate(dev, d_in, d_text, units, 1)))
-            gpu_done = waiter.submit(lambda: (dev.sync(), time.perf_counter())[1])
-        # CPU files meanwhile: sub-batches through two pinned stages, each
-        # copied to HBM on the copy stream while the next one inflates
-        c_bytes = 0
-        pend = [None, None]
-        i = sb = 0
-        while i < len(on_cpu):
-            grp, room = [], 0
-            while i < len(on_cpu) and (not grp or room + _align(caps_[on_cpu[i]]) <= STAGE):
-                grp.append(on_cpu[i])
-                room += _align(caps_[on_cpu[i]])
-                i += 1
-            j = sb % 2
-            sb += 1
-            if pend[j] is not None:
-                pend[j].result()
-            stage = stages[j].get(room + 256)
-            soff = np.zeros(len(grp) + 1, np.int64)
-            soff[1:] = np.cumsum([_align(caps_[k]) for k in grp])
-
-            def one(t, grp=grp, stage=stage, soff=soff):
-                k = grp[t]
-                v = buf[off[k]:off[k] + sizes[fs[k]]]
-                return _abi.gunzip_host(v, stage[soff[t]:soff[t] + caps_[k]], with_crc=True)
-            res = list(pool.map(one, range(len(grp))))
-            for t, k in enumerate(grp):
-                gst[k], tlen[k], hcrc[k] = res[t]
-                c_bytes += int(tlen[k])
-
-            def h2d(grp=grp, stage=stage, soff=soff, res=res):
-                for t, k in enumerate(grp):
-                    if res[t][0] == 0 and res[t][1]:
-                        call("grid_h2d", cdev.ctx, d_text.ptr + int(toff[k]), stage.ctypes.data + int(soff[t]),
-                             int(res[t][1]))
-            pend[j] = copier.submit(h2d)
-        t_cpu = time.perf_counter() - t0
-        for p_ in pend:
-            if p_ is not None:
-                p_.result()
-        if on_cpu and XSTREAM_WAIT:
-            # the parse kernels on dev's stream read text the copy stream wrote
-            # over d_text -- lines the previous batch's kernels had cached: order
-            # the stream behind the copies through the runtime (event + wait), not
-            # through the host's view of their completion alone
-            call("grid_stream_after", dev.ctx, cdev.ctx)
-        hk = [k for k in on_cpu if gst[k] == 0 and tlen[k] > 0]
-        if hk:
-            # the guard: the host-inflated text as it sits in HBM against the CRC
-            # of its gzip trailers, read on dev's stream (where the parse runs)
-            if AFTER_HOST_TEXT is not None:
-                AFTER_HOST_TEXT(dev, d_text, toff, hk)
-            got = _abi.text_crc32(dev, d_text.ptr, toff[hk], tlen[hk])
-            bad = [fs[k] for k, c in zip(hk, got) if int(c) != int(hcrc[k])]
-            if bad:
-                raise DeviceIngestUnsupported(f"{paths[bad[0]]}: its text in HBM does not match its gzip CRC "
-                                              f"({len(bad)} host-inflated file(s))")
-        g_mem = g_whole = 0
-        t_gpu = 0.0
-        if launched:
-            t_gpu = gpu_done.result() - t0
-            for kind, ks, owner, (_d, _mem, st, ln, _nm) in launched:
-                ust, uln = st.numpy(), ln.numpy()
-                if kind == "whole":
-                    gst[ks], tlen[ks] = ust, uln
-                    g_whole = max(g_whole, int(uln.max()))
-                else:
-                    bad = np.zeros(nb, np.int32)
-                    # a member past its BGZF size is corrupt (dropped), not several members
-                    np.maximum.at(bad, owner, np.where(ust == _abi.GZ_ESPACE, _abi.GZ_EDATA, ust))
-                    tot = np.zeros(nb, np.int64)
-                    np.add.at(tot, owner, uln)
-                    gst[ks], tlen[ks] = bad[ks], tot[ks]
-                    g_mem += int(uln.sum())
-        split.learn(g_mem, g_whole, t_gpu, c_bytes, t_cpu)
-        if TRACE:
-            import sys
-            print(f"[ingest] batch files gpu {len(on_gpu)} cpu {len(on_cpu)} text gpu {g_mem + g_whole:.3e} "
-                  f"cpu {c_bytes:.3e} B  t_gpu {t_gpu:.3f} t_cpu {t_cpu:.3f} s  rates gpu {split.gpu:.3e} "
-                  f"cpu/thread {split.cpu:.3e} B/s", file=sys.stderr, flush=True)
-        return gst, tlen
-
+    in_need = 256 + max((int(align(np.maximum(sizes[b], 1)).sum()) for b in batches), default=0)
+    host = _Host(dev, paths, sizes, batches, threads)
     K = kidx = Q = None
     nK = ref_nlines = 0
     if ref is not None:                    # the key list of another rank's reference file
@@ -741,21 +663,18 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
         ref_nlines = int(ref_nlines)
         Q = dev.alloc((max(nfiles, 1), max(nK, 1)), np.int32)
         call("grid_fill_i32", dev.ctx, Q.ptr, max(nfiles, 1) * max(nK, 1), _abi.MISSING)
-    d_text = None
-    d_ins = [None, None]
-    pipe = None
-    pending = rpool.submit(read_batch, 0) if batches else None
+    d_text, d_ins, pipe = None, [None, None], None
+    pending = host.rpool.submit(host.read, 0) if batches else None
     try:
         for bi, fs in enumerate(batches):
             t_w = time.perf_counter()
             buf, off, caps, members = pending.result()
-            pending = rpool.submit(read_batch, bi + 1) if bi + 1 < len(batches) else None
+            pending = host.rpool.submit(host.read, bi + 1) if bi + 1 < len(batches) else None
             nb = len(fs)
             caps_ = np.array([c[0] if c else 0 for c in caps], np.int64)
             gz = np.array([c is not None for c in caps])
-            tcap = np.array([_align(max(c, 1), 256) for c in caps_], np.int64)
             toff = np.zeros(nb + 1, np.int64)
-            toff[1:] = np.cumsum(tcap)
+            toff[1:] = np.cumsum(align(np.maximum(caps_, 1)))
             if toff[-1] > BATCH_TEXT * 2:
                 raise DeviceIngestUnsupported("a batch of files inflates beyond the device text buffer")
             # device buffers sized from the cohort, not from the batch bounds: the
@@ -774,49 +693,29 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
             d_in = d_ins[bi % 2]
             todo = [k for k in range(nb) if gz[k] and sizes[fs[k]] > 0]
             bgzf = {k: members[k] is not None for k in todo}
-            plan = split.plan(todo, caps_, bgzf)
+            plan = host.split.plan(todo, caps_, bgzf)
             if PIPELINE and K is not None and all(bgzf.values()) and not plan[1]:
                 # every file BGZF (what mosdepth writes): the GPU inflates all of
                 # them, and the batch is enqueued behind the previous one
                 if pipe is None:
-                    pipe = _Async(dev, cdev, opts, K, nK, kidx, ref_nlines, Q, general=general)
-                hshare = None
-                if hfrac > 0 and len(todo) > 1:
-                    # every step-th file to the host threads (they start now, beside the
-                    # GPU's work on the previous batch and this batch's copies)
-                    step = max(2, int(round(1.0 / hfrac)))
-                    hfiles = todo[step - 1::step]
-                    so, pos = {}, 0
-                    for k in hfiles:
-                        so[k] = pos
-                        pos += _align(int(caps_[k]))
-                    harr = hstages[bi % 2].get(pos + 256)
-
-                    def run_host(hfiles=hfiles, harr=harr, so=so, buf=buf, off=off, fs=fs, caps_=caps_):
-                        def one(k):
-                            v = buf[off[k]:off[k] + sizes[fs[k]]]
-                            st_, ln_, crc_ = _abi.gunzip_host(v, harr[so[k]:so[k] + int(caps_[k])], with_crc=True)
-                            return k, (int(st_), int(ln_), int(crc_), harr, so[k])
-                        return dict(pool.map(one, hfiles))
-                    hshare = (hfiles, hctl.submit(run_host))
-                h2d_done[bi] = pipe.batch(bi, fs, buf, off, caps_, gz, members, toff, d_in, d_text,
-                                          [sizes[f] for f in fs], hshare=hshare)
-                if TRACE:
-                    import sys
-                    print(f"[ingest] batch {bi}: {nb} files enqueued, wait read {time.perf_counter() - t_w:.3f} s "
-                          f"(at {time.perf_counter() - t_start:.3f})", file=sys.stderr, flush=True)
+                    pipe = _Async(dev, host.cdev, opts, K, nK, kidx, ref_nlines, Q, general=general)
+                host.h2d_done[bi] = pipe.batch(bi, fs, buf, off, caps_, gz, members, toff, d_in, d_text,
+                                               [sizes[f] for f in fs],
+                                               hshare=host.share(bi, todo, buf, off, fs, caps_))
+                _trace("batch {}: {} files enqueued, wait read {:.3f} s (at {:.3f})", bi, nb,
+                       time.perf_counter() - t_w, time.perf_counter() - t_start)
                 continue
             if pipe is not None:
                 pipe.drain()
             t_b = time.perf_counter()
-            gst, tlen = inflate(buf, off, fs, caps_, gz, members, toff, d_in, d_text, plan)
+            gst, tlen = host.inflate(buf, off, fs, caps_, gz, members, toff, d_in, d_text, plan)
             t_i = time.perf_counter()
             for k, f in enumerate(fs):
                 if gst[k] == _abi.GZ_ESPACE:
                     raise DeviceIngestUnsupported(f"{paths[f]}: several gzip members (text size unknown)")
                 status[f] = 0 if gst[k] == 0 else 1        # 1: failed (the reference drops the sample)
             okb = [k for k in range(nb) if gst[k] == 0 and tlen[k] > 0]
-            cfile, cstart, cfirst, nch = _chunks(okb, tlen)
+            chunks = cfile, cstart, cfirst, nch = chunk_table(okb, tlen)
             if nch == 0:
                 continue
             d_tl, d_toff = dev.upload(tlen), dev.upload(toff[:nb])
@@ -827,42 +726,8 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
             call("grid_md_count", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, nch, d_cfile.ptr, d_cstart.ptr,
                  d_cfirst.ptr, len(okb), cnl.ptr, cline0.ptr, bflags.ptr, None)
             if K is None:
-                # the reference key list: the first batch's file with the most
-                # text (a short or truncated file sorted first
-                # no longer sends the cohort to the host parser; K must hold
-                # every later file's keys, which the largest file does)
-                ri = int(np.argmax(tlen[okb]))
-                r = okb[ri]
-                c0, c1 = int(cfirst[ri]), int(cfirst[ri + 1])
-                rc_file = np.zeros(c1 - c0, np.int32) + r
-                cl = cline0.numpy()[c0:c1]
-                nl = cnl.numpy()[c0:c1]
-                tail = np.zeros(1, np.uint8)
-                call("grid_d2h", dev.ctx, tail.ctypes.data, d_text.ptr + int(toff[r] + tlen[r] - 1), 1)
-                ref_nlines = int(cl[-1] + nl[-1]) + (0 if tail[0] == 10 else 1)
-                kline = dev.alloc(max(ref_nlines, 1), np.uint8)
-                keys_line = dev.alloc((max(ref_nlines, 1), 2), np.int64)
-                K = dev.alloc((max(ref_nlines, 1), 2), np.int64)
-                kidx = dev.alloc(max(ref_nlines, 1), np.int32)
-                h_nK, h_uns = C.c_int64(), C.c_int32()
-                d_rcf, d_rcs, d_rcl = dev.upload(rc_file), dev.upload(cstart[c0:c1]), dev.upload(cl)
-                if general:
-                    if ref_nlines >= 1 << 31:
-                        raise DeviceIngestUnsupported(f"{paths[fs[r]]}: {_flag_reason(_abi.MD_LINES)}")
-                    # K: the kept keys sorted and de-duplicated, any order, any repeats
-                    call("grid_md_parse_ref_general", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
-                         d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
-                         kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK))
-                else:
-                    call("grid_md_parse_ref", dev.ctx, d_text.ptr, d_toff.ptr, d_tl.ptr, c1 - c0, d_rcf.ptr,
-                         d_rcs.ptr, d_rcl.ptr, C.byref(opts), bflags.ptr, ref_nlines,
-                         kline.ptr, keys_line.ptr, K.ptr, kidx.ptr, C.byref(h_nK), C.byref(h_uns))
-                del kline, keys_line
-                if h_uns.value:
-                    raise DeviceIngestKeys("the reference file's keys are not strictly increasing")
-                nK = h_nK.value
-                if nK == 0:
-                    raise DeviceIngestUnsupported("the reference file keeps no record")
+                K, kidx, nK, ref_nlines = _reference_keys(dev, opts, general, paths, fs, okb, tlen, toff, chunks, cnl,
+                                                          cline0, d_text, d_toff, d_tl, bflags)
                 if keys_only:
                     break
                 Q = dev.alloc((nfiles, nK), np.int32)
@@ -879,11 +744,8 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
             kept_h = kept.numpy()
             kept_h[np.asarray(fs)] += bkv
             kept.copy_from(kept_h)
-            if TRACE:
-                import sys
-                print(f"[ingest] batch {bi}: {nb} files, wait read {t_b - t_w:.3f} inflate {t_i - t_b:.3f} "
-                      f"parse {time.perf_counter() - t_i:.3f} s (at {time.perf_counter() - t_start:.3f})",
-                      file=sys.stderr, flush=True)
+            _trace("batch {}: {} files, wait read {:.3f} inflate {:.3f} parse {:.3f} s (at {:.3f})", bi, nb, t_b - t_w,
+                   t_i - t_b, time.perf_counter() - t_i, time.perf_counter() - t_start)
         if pipe is not None:
             t_d = time.perf_counter()
             pipe.drain()
@@ -892,9 +754,7 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
             kept_h = kept.numpy()
             kept_h += pipe.kept_total(nfiles)
             kept.copy_from(kept_h)
-            if TRACE:
-                import sys
-                print(f"[ingest] pipeline drained in {time.perf_counter() - t_d:.3f} s", file=sys.stderr, flush=True)
+            _trace("pipeline drained in {:.3f} s", time.perf_counter() - t_d)
     finally:
         if pending is not None:
             try:
@@ -903,57 +763,22 @@ def ingest_device(dev, paths, prefix, window, excluded, min_depth, max_depth, th
                 pass
         if pipe is not None:
             pipe.close()
-        rpool.shutdown(wait=True)
-        iopool.shutdown(wait=True)
-        pool.shutdown(wait=True)
-        copier.shutdown(wait=True)
-        waiter.shutdown(wait=True)
-        hctl.shutdown(wait=True)
-        cdev.close()
-    if TRACE:
-        import sys
-        print(f"[ingest] batches done (threads joined, copy context closed) at {time.perf_counter() - t_start:.3f} s",
-              file=sys.stderr, flush=True)
+        host.close()
+    _trace("batches done (threads joined, copy context closed) at {:.3f} s", time.perf_counter() - t_start)
     # the batches' device buffers stay cached on the context (Device.cached,
     # names "ingest_*") and the host staging in _STAGING until
     # device.release_ingest_buffers() -- the end of the run or of a standalone
     # step 4 -- since their release holds the HIP runtime for a fraction of a
     # second; here only this function's references go
     d_ins = d_text = d_in = pipe = None
-    if TRACE:
-        import sys
-        print(f"[ingest] input/text buffers freed at {time.perf_counter() - t_start:.3f} s", file=sys.stderr,
-              flush=True)
+    _trace("input/text buffers freed at {:.3f} s", time.perf_counter() - t_start)
     if keys_only:
-        if K is None:
-            return None
-        return K.numpy()[:nK].copy(), kidx.numpy()[:max(ref_nlines, 0)].copy(), ref_nlines
+        return None if K is None else (K.numpy()[:nK].copy(), kidx.numpy()[:max(ref_nlines, 0)].copy(), ref_nlines)
     if not finish:
         return Q, nK, status, kept.numpy()[:nfiles].copy()
     if K is None:
         return [], [], None, status
-    rows = np.array([f for f in range(nfiles) if status[f] == 0], np.int32)
-    mean = dev.alloc(nK, np.float64)
-    valid, cpos = dev.alloc(nK, np.int32), dev.alloc(nK, np.int64)
-    present, nvalid = dev.alloc(max(nfiles, 1), np.uint64), dev.alloc(max(nfiles, 1), np.uint64)
-    m = C.c_int64()
-    if TRACE:
-        import sys
-        print(f"[ingest] finish buffers at {time.perf_counter() - t_start:.3f} s", file=sys.stderr, flush=True)
-    d_rows = dev.upload(rows if rows.size else np.zeros(1, np.int32))
-    call("grid_md_finish", dev.ctx, Q.ptr, nK, nK, nfiles, d_rows.ptr, len(rows), float(min_depth),
-         float(max_depth), mean.ptr, valid.ptr, cpos.ptr, present.ptr, nvalid.ptr, C.byref(m))
-    pres, nval, kh = present.numpy()[:nfiles], nvalid.numpy()[:nfiles], kept.numpy()[:nfiles]
-    if np.any(pres[rows] != kh[rows]):
-        if general:
-            # the integrity guard: every present cell was filled by exactly one line's resolve
-            raise DeviceIngestUnsupported("an unresolved cell in a file's row (general keys)")
-        raise DeviceIngestKeys("a repeated (start, end) key in a file")
-    m = m.value
-    if TRACE:
-        import sys
-        print(f"[ingest] finish done at {time.perf_counter() - t_start:.3f} s", file=sys.stderr, flush=True)
-    return rows, (Q, nK, valid, cpos, K, m), nval, status
+    return _finish(dev, Q, nK, K, kept, status, nfiles, min_depth, max_depth, general, t_start)
 
 
 class Regions(Sequence):
@@ -1004,9 +829,7 @@ def gather(dev, state, row_files, nfiles):
     call("grid_md_gather", dev.ctx, Q.ptr, nK, nK, nfiles, valid.ptr, cpos.ptr, d_dst.ptr, out.ptr,
          max(m, 1), K.ptr, st.ptr, en.ptr)
     regions = Regions(st.numpy()[:m], en.numpy()[:m])
-    if TRACE:
-        import sys
-        print(f"[ingest] gather: {len(row_files)} of {nfiles} rows, {m} of {nK} columns; alloc "
-              f"{t1 - t0:.3f} s, gather {time.perf_counter() - t1:.3f} s", file=sys.stderr, flush=True)
+    _trace("gather: {} of {} rows, {} of {} columns; alloc {:.3f} s, gather {:.3f} s", len(row_files), nfiles, m, nK,
+           t1 - t0, time.perf_counter() - t1)
     out.shape = (len(row_files), m)            # the allocation keeps >= 1 element
     return out, regions

@@ -37,12 +37,10 @@ import numpy as np
 
 from .. import _abi
 from .._abi import call
-from . import ingest_device
-from .ingest_device import _align, _chunks, _staging
+from .gz_batch import CH, READ_THREADS, align, chunk_table, staging
 
 BATCH_IN = 20 << 30             # compressed bytes per batch
 BATCH_TEXT = 48 << 30           # inflated bytes per batch
-READ_THREADS = int(os.environ.get("GRID_INGEST_READ_THREADS", "8"))
 WAVES_PER_CU = 32               # k_inflate: 8 waves on each of a CU's 4 SIMDs (inflate.hip GRID_INFLATE_WPE)
 P = _abi.NT_PREFIX_BYTES
 
@@ -103,7 +101,7 @@ def plan_batches(clen, tlen, batch_in=None, batch_text=None):
     bt = BATCH_TEXT if batch_text is None else batch_text
     batches, cur, cin, ctx = [], [], 0, 0
     for m in range(len(clen)):
-        a, b = _align(max(int(clen[m]), 1)), _align(max(int(tlen[m]), 1))
+        a, b = align(max(int(clen[m]), 1)), align(max(int(tlen[m]), 1))
         if cur and (cin + a > bi or ctx + b > bt):
             batches.append(cur)
             cur, cin, ctx = [], 0, 0
@@ -117,12 +115,9 @@ def plan_batches(clen, tlen, batch_in=None, batch_text=None):
 
 def _cached(dev, name, want, budget):
     """dev.cached(name, want) against a byte budget of new HBM."""
-    old = dev.__dict__.get("_cache", {}).get(name)
-    have = old.nbytes if old is not None else 0
-    if have < want:
-        budget[0] -= want - have
-        if budget[0] < 0:
-            raise DeviceReadUnsupported("the matrix and the batch buffers do not fit in the free HBM")
+    budget[0] -= max(0, want - dev.cached_nbytes(name))
+    if budget[0] < 0:
+        raise DeviceReadUnsupported("the matrix and the batch buffers do not fit in the free HBM")
     return dev.cached(name, want)
 
 
@@ -153,10 +148,9 @@ def read(dev, path, threads=None, timings=None):
     if frow[0] != 0 or np.any(np.diff(frow) <= 0) or frow[-1] >= N:
         raise DeviceReadUnsupported("member first rows are not running row counts")
     batches = plan_batches(clen, isize)
-    al = lambda v: (np.maximum(v, 1) + 255) // 256 * 256
-    in_need = 256 + max(int(al(clen[b]).sum()) for b in batches)
-    text_need = 256 + P + max(int(al(isize[b]).sum()) for b in batches)
-    nchunk_max = max(int((-(-isize[b] // ingest_device.CH)).sum()) for b in batches)
+    in_need = 256 + max(int(align(np.maximum(clen[b], 1)).sum()) for b in batches)
+    text_need = 256 + P + max(int(align(np.maximum(isize[b], 1)).sum()) for b in batches)
+    nchunk_max = max(int((-(-isize[b] // CH)).sum()) for b in batches)
     small = N * (8 + P) + 64 * nchunk_max + 256 * max(len(b) for b in batches) + (64 << 20)
     free, _total = dev.mem_info()
     budget = [int(free) - N * R * 4 - small]
@@ -168,7 +162,7 @@ def read(dev, path, threads=None, timings=None):
     zq = dev.alloc((N, R), np.int32)
     rowoff = dev.alloc(N, np.int64).fill_bytes(0xFF)
     pre = dev.zeros((N, P), np.uint8)
-    stag = [_staging(f"in{p}", BATCH_IN + 512) for p in range(nin)]
+    stag = [staging(f"in{p}", BATCH_IN + 512) for p in range(nin)]
     pool = ThreadPoolExecutor(max(1, READ_THREADS))
     rpool = ThreadPoolExecutor(1)
     cdev = _abi.Device(dev.index)             # the copy stream
@@ -179,7 +173,7 @@ def read(dev, path, threads=None, timings=None):
         t0 = time.perf_counter()
         ms = batches[bi]
         ioff = np.zeros(len(ms) + 1, np.int64)
-        ioff[1:] = np.cumsum(al(clen[ms]))
+        ioff[1:] = np.cumsum(align(np.maximum(clen[ms], 1)))
         buf = stag[bi % 2].get(int(ioff[-1]) + 256)
         mv = memoryview(buf)
 
@@ -211,8 +205,8 @@ def read(dev, path, threads=None, timings=None):
             nb = len(ms)
             tlen = isize[ms].astype(np.int64)
             toff = np.zeros(nb + 1, np.int64)
-            toff[1:] = np.cumsum(al(tlen))
-            cfile, cstart, cfirst, nch = _chunks(np.arange(nb), tlen)
+            toff[1:] = np.cumsum(align(np.maximum(tlen, 1)))
+            cfile, cstart, cfirst, nch = chunk_table(np.arange(nb), tlen)
             up = [dev.upload(np.ascontiguousarray(a)) for a in
                   (ioff[:-1], clen[ms].astype(np.int64), toff[:-1], tlen, frow[ms].astype(np.int64), cfile, cstart,
                    cfirst)]

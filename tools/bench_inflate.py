@@ -20,6 +20,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from grid_amd import _abi  # noqa: E402
+from grid_amd.utils.gz_batch import align, fold_members, member_units  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--files", type=int, default=256)
@@ -62,27 +63,18 @@ dev = _abi.Device(0)
 dev.set_stream(torch.cuda.current_stream())
 res = []
 if a.units:
-    # every member its own stream, text back to back per file (ingest_device.inflate)
+    # every member its own stream, text back to back per file (the ingest's table: gz_batch.member_units)
     assert a.bgzf
-    io, il, oo, oc, fo = [], [], [], [], []
-    pos = opos = 0
-    for b in files:
-        ms, ml, mi = _abi.gz_members(b)
-        cum = np.zeros(len(mi), np.int64)
-        np.cumsum(mi[:-1], out=cum[1:])
-        io.append(pos + ms)
-        il.append(ml)
-        oo.append(opos + cum)
-        oc.append(mi.astype(np.int64))
-        fo.append(opos)
-        pos += -(-len(b) // 256) * 256
-        opos += -(-int(mi.sum()) // 256) * 256
-    io, il, oo, oc = (np.concatenate(x) for x in (io, il, oo, oc))
+    members = [_abi.gz_members(b) for b in blobs]
+    members = [members[i % len(blobs)] for i in range(a.files)]
+    ioff, off = np.zeros(a.files + 1, np.int64), np.zeros(a.files + 1, np.int64)
+    ioff[1:] = np.cumsum([align(len(b)) for b in files])
+    off[1:] = np.cumsum([align(int(m[2].sum())) for m in members])
+    io, il, oo, oc, owner = member_units(members, ioff, off, range(a.files))
+    pos, opos = int(ioff[-1]), int(off[-1])
     src = np.zeros(pos + 256, np.uint8)
-    p = 0
-    for b in files:
+    for p, b in zip(ioff, files):
         src[p:p + len(b)] = np.frombuffer(b, np.uint8)
-        p += -(-len(b) // 256) * 256
     d_src = dev.upload(src)
     d = [dev.upload(x) for x in (io, il, oo, oc)]
     nu = len(io)
@@ -98,11 +90,8 @@ if a.units:
         res.append(time.perf_counter() - t1)
     ust, uln = st_d.numpy(), ln_d.numpy()
     assert (ust == 0).all(), np.unique(ust, return_counts=True)
-    owner = np.concatenate([np.full(len(_abi.gz_members(b)[0]), f) for f, b in enumerate(files)])
-    ln = np.bincount(owner, weights=uln, minlength=len(files)).astype(np.int64)
-    st = np.zeros(len(files), np.int32)
-    nm = np.bincount(owner, minlength=len(files))
-    off = np.array(fo, np.int64)
+    st, ln = fold_members(a.files, owner, ust, uln)
+    nm = np.bincount(owner, minlength=a.files)
 else:
     for rep in range(3):
         torch.cuda.synchronize()
