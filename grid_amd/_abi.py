@@ -102,6 +102,9 @@ _SIGS = {
                       _i32, _i32],
     "grid_hi_phase_batch": [_vp, _i64, _vp, _i64, _i32, _i64, _i64, _i32, _i32],
     "grid_hi_pack_batch": [_vp, _i64, _vp, _i64],
+    # return a route, not a status (hi_phase_route below)
+    "grid_hi_phase_route": [_i64, _i32, _i32, _i32],
+    "grid_hi_phase_batch_route": [_i64, _i32, _i32, _i32],
     "grid_write_normalized_gz": [C.c_char_p, _i64, _i64, C.c_char_p, _vp, _vp, _vp, _vp, _i64, _i32, _i32],
     "grid_read_normalized_gz": [C.c_char_p, _i32, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64)],
     "grid_write_normalized_gz_dev": [_vp, C.c_char_p, _i64, _i64, C.c_char_p, _vp, _vp, _vp, _vp, _i64, _i32, _i32,
@@ -763,6 +766,20 @@ def hi_levels(off: np.ndarray, nbr: np.ndarray):
 
 PACK_CAP = 16
 HI_UNIT_WEIGHTS, HI_LEGACY, HI_PAIRED = 1, 2, 4     # grid_hi_phase flags
+HI_PH2 = 8
+# include/grid_abi.h grid_hi_route: the kernel a phasing launch runs
+(HI_ROUTE_PHASE4, HI_ROUTE_PH2_SPLIT_LDS, HI_ROUTE_PH2_PAIRED_LDS, HI_ROUTE_PH_LEGACY_LDS, HI_ROUTE_PH2_SPLIT_GLOBAL,
+ HI_ROUTE_PH_LEGACY_GLOBAL) = range(1, 7)
+
+
+def hi_phase_route(n: int, nlevels: int, flags: int, max_list: int, batch: bool = False):
+    """(kernel, CAPT) that grid_hi_phase -- ``batch``: grid_hi_phase_batch --
+    launches for these sizes and flags (host only; CAPT 0: a legacy kernel)."""
+    f = load().grid_hi_phase_batch_route if batch else load().grid_hi_phase_route
+    r = f(int(n), int(nlevels), int(flags), int(max_list))
+    if r < 0:
+        raise GridNativeError(f"grid_hi_phase_route: bad arguments ({n}, {nlevels}, {flags}, {max_list})")
+    return r & 0xFF, r >> 8
 
 
 def hi_schedule(off: np.ndarray, nbr: np.ndarray, w: np.ndarray, packed_w: bool = True):

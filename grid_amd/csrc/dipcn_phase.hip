@@ -1130,6 +1130,37 @@ __global__ __launch_bounds__(256) void k_phase4(int64_t n, const double *__restr
   if (tid == 0) *mean_out = mean;
 }
 
+// The kernel a phasing launch runs, its list capacity and its dynamic LDS, from
+// the launch's sizes and flags alone (host, no device).  grid_hi_phase and
+// grid_hi_phase_batch launch what this returns and grid_hi_phase_route /
+// grid_hi_phase_batch_route report it, so a test can assert which kernel it ran.
+struct HiRoute {
+  int kern;      // grid_hi_route
+  int capt;      // 8 / 16; 0: the legacy kernels have no register capacity
+  size_t lds;    // dynamic LDS bytes of the launch
+};
+HiRoute hi_route(int64_t n, int32_t nlevels, int32_t flags, int32_t max_list, bool has_phase4) {
+  constexpr size_t LDS_MAX = 120 * 1024;
+  const size_t lds = (size_t)3 * n * sizeof(double) + (size_t)(nlevels + 1) * 4 + (size_t)n;
+  // k_phase2 adds its chunk table (<= nlevels + n/PT + 1 entries, 16-B aligned)
+  const size_t lds2 = lds + 32 + (size_t)(nlevels + n / PT + 2) * 8;
+  const size_t lds_g = 32 + (size_t)(nlevels + n / PT + 2) * 8;   // hap in global memory
+  // k_phase4's LDS: hap, irr, level offsets, flags, then a 16-B aligned int4 chunk table
+  const size_t lds4 = ((lds + 15) & ~(size_t)15) + (size_t)(nlevels + n / 128 + 2) * 16;
+  const int capt = max_list <= 8 ? 8 : 16;   // CAPT covers the longest list when it can
+  if (has_phase4 && lds4 <= LDS_MAX && !(flags & (GRID_HI_LEGACY | GRID_HI_PAIRED | GRID_HI_PH2)))
+    return {GRID_HI_ROUTE_PHASE4, capt, lds4};
+  if (lds2 <= LDS_MAX && !(flags & GRID_HI_LEGACY))
+    // default: 512 lanes, one haplotype per lane (256 entries per chunk);
+    // GRID_HI_PAIRED: 256 lanes, both haplotypes per lane
+    return {(flags & GRID_HI_PAIRED) ? GRID_HI_ROUTE_PH2_PAIRED_LDS : GRID_HI_ROUTE_PH2_SPLIT_LDS, capt, lds2};
+  if (lds <= LDS_MAX) return {GRID_HI_ROUTE_PH_LEGACY_LDS, 0, lds};
+  // hap in global memory, split-lane register kernel (LDS: the chunk table)
+  if (!(flags & (GRID_HI_LEGACY | GRID_HI_PAIRED)) && lds_g <= LDS_MAX)
+    return {GRID_HI_ROUTE_PH2_SPLIT_GLOBAL, capt, lds_g};
+  return {GRID_HI_ROUTE_PH_LEGACY_GLOBAL, 0, 0};
+}
+
 }  // namespace
 
 extern "C" {
@@ -1203,17 +1234,13 @@ int grid_hi_phase(grid_ctx *ctx, int64_t n, const double *d_irr, const int64_t *
                   int32_t max_list) {
   REQUIRE(ctx && n >= 0 && n_iters >= 0 && nlevels >= 0 && max_list >= 0, "bad args");
   if (n == 0) return GRID_OK;
-  const size_t lds = (size_t)3 * n * sizeof(double) + (size_t)(nlevels + 1) * 4 + (size_t)n;
-  // k_phase2 adds its chunk table (<= nlevels + n/PT + 1 entries, 16-B aligned)
-  const size_t lds2 = lds + 32 + (size_t)(nlevels + n / PT + 2) * 8;
-  const size_t lds_g = 32 + (size_t)(nlevels + n / PT + 2) * 8;   // hap in global memory
   const bool unitw = flags & GRID_HI_UNIT_WEIGHTS;
-  // k_phase4's LDS: hap, irr, level offsets, flags, then a 16-B aligned int4 chunk table
-  const size_t lds4 = ((lds + 15) & ~(size_t)15) + (size_t)(nlevels + n / 128 + 2) * 16;
-  if (lds4 <= 120 * 1024 && !(flags & (GRID_HI_LEGACY | GRID_HI_PAIRED | GRID_HI_PH2))) {
-    auto kern = unitw ? (max_list <= 8 ? k_phase4<true, 8> : k_phase4<true, 16>)
-                      : (max_list <= 8 ? k_phase4<false, 8> : k_phase4<false, 16>);
-    int slot = (unitw ? 2 : 0) + (max_list <= 8 ? 0 : 1);
+  const HiRoute rt = hi_route(n, nlevels, flags, max_list, true);
+  const bool c8 = rt.capt == 8;
+  if (rt.kern == GRID_HI_ROUTE_PHASE4) {
+    auto kern = unitw ? (c8 ? k_phase4<true, 8> : k_phase4<true, 16>)
+                      : (c8 ? k_phase4<false, 8> : k_phase4<false, 16>);
+    int slot = (unitw ? 2 : 0) + (c8 ? 0 : 1);
 #ifdef GRID_PROBES
     const char *pe4 = getenv("GRID_PHASE_PROBE");
     const int probe4 = pe4 ? atoi(pe4) : 0;
@@ -1228,18 +1255,16 @@ int grid_hi_phase(grid_ctx *ctx, int64_t n, const double *d_irr, const int64_t *
       HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
       attr4[slot] = true;
     }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(256), lds4, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr, n_iters,
+    hipLaunchKernelGGL(kern, dim3(1), dim3(256), rt.lds, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr, n_iters,
                        d_order, d_loff, nlevels, d_pk_nbr, d_pk_w, d_pk_cnt, d_hap, d_imp, d_mean);
-  } else if (lds2 <= 120 * 1024 && !(flags & GRID_HI_LEGACY)) {
-    // register-pipelined kernel; CAPT covers the longest list when it can
-    // default: 512 lanes, one haplotype per lane (256 entries per chunk);
-    // GRID_HI_PAIRED: 256 lanes, both haplotypes per lane
-    const bool split = !(flags & GRID_HI_PAIRED);
+  } else if (rt.kern == GRID_HI_ROUTE_PH2_SPLIT_LDS || rt.kern == GRID_HI_ROUTE_PH2_PAIRED_LDS) {
+    // register-pipelined kernel
+    const bool split = rt.kern == GRID_HI_ROUTE_PH2_SPLIT_LDS;
     constexpr int NS = 2 * PT;
-    auto kern = split ? (unitw ? (max_list <= 8 ? k_phase2<true, 8, 0, NS, true> : k_phase2<true, 16, 0, NS, true>)
-                               : (max_list <= 8 ? k_phase2<false, 8, 0, NS, true> : k_phase2<false, 16, 0, NS, true>))
-                      : (unitw ? (max_list <= 8 ? k_phase2<true, 8> : k_phase2<true, 16>)
-                               : (max_list <= 8 ? k_phase2<false, 8> : k_phase2<false, 16>));
+    auto kern = split ? (unitw ? (c8 ? k_phase2<true, 8, 0, NS, true> : k_phase2<true, 16, 0, NS, true>)
+                               : (c8 ? k_phase2<false, 8, 0, NS, true> : k_phase2<false, 16, 0, NS, true>))
+                      : (unitw ? (c8 ? k_phase2<true, 8> : k_phase2<true, 16>)
+                               : (c8 ? k_phase2<false, 8> : k_phase2<false, 16>));
 #ifdef GRID_PROBES
     // tools build only -- GRID_PHASE_PROBE timing probes (wrong results):
     // 1 = no list prefetch, 2 = no arithmetic, 3 = neither
@@ -1252,35 +1277,34 @@ int grid_hi_phase(grid_ctx *ctx, int64_t n, const double *d_irr, const int64_t *
     const int probe = 0;
 #endif
     static bool attr2[11] = {};
-    const int slot = probe ? 3 + probe : (split ? 7 : 0) + (unitw ? 2 : 0) + (max_list <= 8 ? 0 : 1);
+    const int slot = probe ? 3 + probe : (split ? 7 : 0) + (unitw ? 2 : 0) + (c8 ? 0 : 1);
     if (!attr2[slot]) {
       HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
       attr2[slot] = true;
     }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(split && !probe ? NS : PT), lds2, ctx->stream, n, d_irr, d_off, d_nbr,
+    hipLaunchKernelGGL(kern, dim3(1), dim3(split && !probe ? NS : PT), rt.lds, ctx->stream, n, d_irr, d_off, d_nbr,
                        d_w, min_nbr, n_iters, d_order, d_loff, nlevels, d_pk_nbr, d_pk_w, d_pk_cnt, d_hap, d_imp, d_mean);
-  } else if (lds <= 120 * 1024) {
+  } else if (rt.kern == GRID_HI_ROUTE_PH_LEGACY_LDS) {
     static bool attr = false;
     if (!attr) {
       HIPCHK(hipFuncSetAttribute((const void *)k_phase<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  120 * 1024));
       attr = true;
     }
-    hipLaunchKernelGGL(k_phase<true>, dim3(1), dim3(PT), lds, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr,
+    hipLaunchKernelGGL(k_phase<true>, dim3(1), dim3(PT), rt.lds, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr,
                        n_iters, d_order, d_loff, nlevels, d_pk_nbr, d_pk_w, d_pk_cnt, d_hap, d_imp, d_mean);
-  } else if (!(flags & (GRID_HI_LEGACY | GRID_HI_PAIRED)) && lds_g <= 120 * 1024) {
-    // hap in global memory, split-lane register kernel (LDS: the chunk table)
+  } else if (rt.kern == GRID_HI_ROUTE_PH2_SPLIT_GLOBAL) {
     constexpr int NS = 2 * PT;
-    auto kern = unitw ? (max_list <= 8 ? k_phase2<true, 8, 0, NS, true, true> : k_phase2<true, 16, 0, NS, true, true>)
-                      : (max_list <= 8 ? k_phase2<false, 8, 0, NS, true, true>
+    auto kern = unitw ? (c8 ? k_phase2<true, 8, 0, NS, true, true> : k_phase2<true, 16, 0, NS, true, true>)
+                      : (c8 ? k_phase2<false, 8, 0, NS, true, true>
                                        : k_phase2<false, 16, 0, NS, true, true>);
     static bool attrg[4] = {};
-    const int slot = (unitw ? 2 : 0) + (max_list <= 8 ? 0 : 1);
+    const int slot = (unitw ? 2 : 0) + (c8 ? 0 : 1);
     if (!attrg[slot]) {
       HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
       attrg[slot] = true;
     }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(NS), lds_g, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr, n_iters,
+    hipLaunchKernelGGL(kern, dim3(1), dim3(NS), rt.lds, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr, n_iters,
                        d_order, d_loff, nlevels, d_pk_nbr, d_pk_w, d_pk_cnt, d_hap, d_imp, d_mean);
   } else {
     hipLaunchKernelGGL(k_phase<false>, dim3(1), dim3(PT), 0, ctx->stream, n, d_irr, d_off, d_nbr, d_w, min_nbr,
@@ -1333,55 +1357,66 @@ int grid_hi_phase_batch(grid_ctx *ctx, int64_t n_loci, const grid_hi_locus *d_lo
   REQUIRE(n_loci <= 0x7fffffff, "too many loci");
   if (n_loci == 0 || max_n == 0) return GRID_OK;
   REQUIRE(d_loci, "d_loci is NULL");
-  const size_t lds = (size_t)3 * max_n * sizeof(double) + (size_t)(max_nlev + 1) * 4 + (size_t)max_n;
-  const size_t lds2 = lds + 32 + (size_t)(max_nlev + max_n / PT + 2) * 8;
-  const size_t lds_g = 32 + (size_t)(max_nlev + max_n / PT + 2) * 8;
   const bool unitw = flags & GRID_HI_UNIT_WEIGHTS;
-  if (lds2 <= 120 * 1024 && !(flags & GRID_HI_LEGACY)) {
-    const bool split = !(flags & GRID_HI_PAIRED);
+  const HiRoute rt = hi_route(max_n, max_nlev, flags, max_list, false);
+  const bool c8 = rt.capt == 8;
+  if (rt.kern == GRID_HI_ROUTE_PH2_SPLIT_LDS || rt.kern == GRID_HI_ROUTE_PH2_PAIRED_LDS) {
+    const bool split = rt.kern == GRID_HI_ROUTE_PH2_SPLIT_LDS;
     constexpr int NS = 2 * PT;
-    auto kern = split ? (unitw ? (max_list <= 8 ? k_phase2_batch<true, 8, NS, true> : k_phase2_batch<true, 16, NS, true>)
-                               : (max_list <= 8 ? k_phase2_batch<false, 8, NS, true>
+    auto kern = split ? (unitw ? (c8 ? k_phase2_batch<true, 8, NS, true> : k_phase2_batch<true, 16, NS, true>)
+                               : (c8 ? k_phase2_batch<false, 8, NS, true>
                                                 : k_phase2_batch<false, 16, NS, true>))
-                      : (unitw ? (max_list <= 8 ? k_phase2_batch<true, 8> : k_phase2_batch<true, 16>)
-                               : (max_list <= 8 ? k_phase2_batch<false, 8> : k_phase2_batch<false, 16>));
+                      : (unitw ? (c8 ? k_phase2_batch<true, 8> : k_phase2_batch<true, 16>)
+                               : (c8 ? k_phase2_batch<false, 8> : k_phase2_batch<false, 16>));
     static bool attr[8] = {};
-    const int slot = (split ? 4 : 0) + (unitw ? 2 : 0) + (max_list <= 8 ? 0 : 1);
+    const int slot = (split ? 4 : 0) + (unitw ? 2 : 0) + (c8 ? 0 : 1);
     if (!attr[slot]) {
       HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
       attr[slot] = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_loci), dim3(split ? NS : PT), lds2, ctx->stream, d_loci, min_nbr,
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_loci), dim3(split ? NS : PT), rt.lds, ctx->stream, d_loci, min_nbr,
                        n_iters);
-  } else if (lds <= 120 * 1024) {
+  } else if (rt.kern == GRID_HI_ROUTE_PH_LEGACY_LDS) {
     static bool attr = false;
     if (!attr) {
       HIPCHK(hipFuncSetAttribute((const void *)k_phase_batch<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  120 * 1024));
       attr = true;
     }
-    hipLaunchKernelGGL(k_phase_batch<true>, dim3((unsigned)n_loci), dim3(PT), lds, ctx->stream, d_loci, min_nbr,
+    hipLaunchKernelGGL(k_phase_batch<true>, dim3((unsigned)n_loci), dim3(PT), rt.lds, ctx->stream, d_loci, min_nbr,
                        n_iters);
-  } else if (!(flags & (GRID_HI_LEGACY | GRID_HI_PAIRED)) && lds_g <= 120 * 1024) {
+  } else if (rt.kern == GRID_HI_ROUTE_PH2_SPLIT_GLOBAL) {
     // hap in each locus's global output buffer (L2-resident per workgroup)
     constexpr int NS = 2 * PT;
-    auto kern = unitw ? (max_list <= 8 ? k_phase2_batch<true, 8, NS, true, true>
+    auto kern = unitw ? (c8 ? k_phase2_batch<true, 8, NS, true, true>
                                        : k_phase2_batch<true, 16, NS, true, true>)
-                      : (max_list <= 8 ? k_phase2_batch<false, 8, NS, true, true>
+                      : (c8 ? k_phase2_batch<false, 8, NS, true, true>
                                        : k_phase2_batch<false, 16, NS, true, true>);
     static bool attrg[4] = {};
-    const int slot = (unitw ? 2 : 0) + (max_list <= 8 ? 0 : 1);
+    const int slot = (unitw ? 2 : 0) + (c8 ? 0 : 1);
     if (!attrg[slot]) {
       HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
       attrg[slot] = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_loci), dim3(NS), lds_g, ctx->stream, d_loci, min_nbr, n_iters);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_loci), dim3(NS), rt.lds, ctx->stream, d_loci, min_nbr, n_iters);
   } else {
     hipLaunchKernelGGL(k_phase_batch<false>, dim3((unsigned)n_loci), dim3(PT), 0, ctx->stream, d_loci, min_nbr,
                        n_iters);
   }
   LAUNCHCHK();
   return GRID_OK;
+}
+
+int grid_hi_phase_route(int64_t n, int32_t nlevels, int32_t flags, int32_t max_list) {
+  if (n < 0 || nlevels < 0 || max_list < 0) return -1;
+  const HiRoute rt = hi_route(n, nlevels, flags, max_list, true);
+  return rt.kern | (rt.capt << 8);
+}
+
+int grid_hi_phase_batch_route(int64_t max_n, int32_t max_nlevels, int32_t flags, int32_t max_list) {
+  if (max_n < 0 || max_nlevels < 0 || max_list < 0) return -1;
+  const HiRoute rt = hi_route(max_n, max_nlevels, flags, max_list, false);
+  return rt.kern | (rt.capt << 8);
 }
 
 }  // extern "C"

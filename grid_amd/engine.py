@@ -382,10 +382,12 @@ def csr_from_lists(hap_nbrs):
 
 
 def phase(dev: Device, irr: np.ndarray, off: np.ndarray, nbr: np.ndarray, w: np.ndarray, min_nbr: int,
-          n_iters: int, legacy: bool = False, paired: bool = False):
+          n_iters: int, legacy: bool = False, paired: bool = False, ph2: bool = False):
     """``legacy`` selects the per-neighbour LDS kernel (k_phase) that larger
     loci run anyway; ``paired`` the register-pipelined kernel with both
-    haplotypes of a sample on one lane (A/B tests; same results)."""
+    haplotypes of a sample on one lane; ``ph2`` the 512-lane split kernel
+    (k_phase2) where k_phase4 would run (A/B tests; same results;
+    _abi.hi_phase_route names the kernel a set of flags runs)."""
     n = len(irr)
     if n == 0:
         return np.zeros(0), np.zeros(0), 0.0
@@ -397,7 +399,8 @@ def phase(dev: Device, irr: np.ndarray, off: np.ndarray, nbr: np.ndarray, w: np.
     hap, imp, mean = dev.alloc(2 * n, F8), dev.alloc(2 * n, F8), dev.alloc(1, F8)
     call("grid_hi_phase", dev.ctx, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, min_nbr, n_iters,
          bufs[4].ptr, bufs[5].ptr, nl, bufs[6].ptr, bufs[7].ptr, bufs[8].ptr, hap.ptr, imp.ptr, mean.ptr,
-         flags | (_abi.HI_LEGACY if legacy else 0) | (_abi.HI_PAIRED if paired else 0), max_list)
+         flags | (_abi.HI_LEGACY if legacy else 0) | (_abi.HI_PAIRED if paired else 0)
+         | (_abi.HI_PH2 if ph2 else 0), max_list)
     return hap.numpy(), imp.numpy(), float(mean.numpy()[0])
 
 

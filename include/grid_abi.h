@@ -485,7 +485,29 @@ int grid_hi_phase(grid_ctx *ctx, int64_t n, const double *d_irr, const int64_t *
 #define GRID_HI_UNIT_WEIGHTS 1   /* every weight is 1.0 (IBS lists): weights are not read */
 #define GRID_HI_LEGACY 2         /* A/B: the previous (per-neighbour LDS round trip) kernel */
 #define GRID_HI_PAIRED 4         /* A/B: register-pipelined kernel with both haplotypes per lane */
-#define GRID_HI_PH2 8            /* A/B: round 5's split-lane kernel (512 lanes) instead of k_phase4 */
+#define GRID_HI_PH2 8            /* A/B: round 5's split-lane kernel (512 lanes) instead of k_phase4;
+                                  * also what runs by default where k_phase4's LDS does not fit and
+                                  * k_phase2's does (many levels).  tests/test_gpu_phase.py drives
+                                  * every case of tests/phase_cases.py through each of these flags. */
+/* Which kernel a launch runs: the choice grid_hi_phase / grid_hi_phase_batch
+ * make from (n, nlevels, flags, max_list) alone -- pure host functions, no
+ * context or device -- and the only copy of those conditions (the launch
+ * functions call them).  Returns a grid_hi_route kernel in the low byte and
+ * the register capacity per list (CAPT, 8 or 16; 0 for the legacy kernels,
+ * which have none) above it, or -1 on bad arguments.  The tests assert the
+ * route before each launch (tests/test_gpu_phase.py) and pin the capacity
+ * thresholds (tests/test_phase_cases_cpu.py). */
+enum grid_hi_route {
+  GRID_HI_ROUTE_PHASE4 = 1,            /* k_phase4: 256 lanes, split, hap in LDS */
+  GRID_HI_ROUTE_PH2_SPLIT_LDS = 2,     /* k_phase2 split (512 lanes), hap in LDS */
+  GRID_HI_ROUTE_PH2_PAIRED_LDS = 3,    /* k_phase2, both haplotypes per lane, hap in LDS */
+  GRID_HI_ROUTE_PH_LEGACY_LDS = 4,     /* k_phase<true> */
+  GRID_HI_ROUTE_PH2_SPLIT_GLOBAL = 5,  /* k_phase2 split, hap in d_hap */
+  GRID_HI_ROUTE_PH_LEGACY_GLOBAL = 6   /* k_phase<false> */
+};
+#define GRID_HI_ROUTE_KERNEL(r) ((r) & 0xff)
+#define GRID_HI_ROUTE_CAPT(r) ((r) >> 8)
+int grid_hi_phase_route(int64_t n, int32_t nlevels, int32_t flags, int32_t max_list);
 
 /* Haplotype-neighbour files -> CSR (host C++; Python text semantics for ASCII
  * input).  ids_nl: the dipCN file's sample IDs joined by '\n' (index = line
@@ -531,6 +553,9 @@ int grid_hi_pack_batch(grid_ctx *ctx, int64_t n_loci, const grid_hi_locus *d_loc
 int grid_hi_phase_batch(grid_ctx *ctx, int64_t n_loci, const grid_hi_locus *d_loci, int64_t max_n,
                         int32_t max_nlev, int64_t min_nbr, int64_t n_iters, int32_t flags,
                         int32_t max_list);
+/* grid_hi_phase_route for the batch launch (which has no k_phase4 and
+ * ignores GRID_HI_PH2). */
+int grid_hi_phase_batch_route(int64_t max_n, int32_t max_nlevels, int32_t flags, int32_t max_list);
 
 /* ---------------------------------------------------- synthetic input
  * Counter-based synthetic cohort (bench/smoke input, not a product path):

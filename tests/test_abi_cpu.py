@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import steps
+from tests.phase_ops import run_levels as _run_levels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
@@ -37,40 +38,6 @@ def test_format_hundredths_matches_python():
     assert _abi.format_hundredths(v) == "\t".join(f"{x / 100:.2f}" for x in v.tolist())
     assert _abi.format_hundredths(np.array([_abi.ZQ_NAN, _abi.ZQ_NEG0], np.int32)) == "NA\t-0.00"
     assert _abi.format_hundredths(np.zeros(0, np.int32)) == ""
-
-
-def _run_levels(irr, hn, min_nbr, iters):
-    """Execute the level schedule in Python (read-all-then-write per level)."""
-    import math
-    from grid_amd import _abi, engine
-    off, nbr, w = engine.csr_from_lists(hn)
-    order, loff, nl = _abi.hi_levels(off, nbr)
-    n = len(irr)
-    assert sorted(order.tolist()) == list(range(n))
-    hap = [float("nan")] * (2 * n)
-    for i in range(n):
-        if len(hn[2 * i]) >= min_nbr and len(hn[2 * i + 1]) >= min_nbr:
-            hap[2 * i] = hap[2 * i + 1] = irr[i] / 2
-    for _ in range(iters):
-        for l in range(nl):
-            upd = []
-            for e in range(loff[l], loff[l + 1]):
-                i = int(order[e])
-                if math.isnan(hap[2 * i]):
-                    continue
-                ws, wv = [1e-9, 1e-9], [0.0, 0.0]
-                for h in range(2):
-                    for nb, wt in hn[2 * i + h]:
-                        v = hap[nb]
-                        if not math.isnan(v):
-                            ws[h] += wt
-                            wv[h] += wt * v
-                m0, m1 = wv[0] / ws[0], wv[1] / ws[1]
-                if m0 + m1 > 0:
-                    upd.append((i, irr[i] * m0 / (m0 + m1), irr[i] * m1 / (m0 + m1)))
-            for i, a, b in upd:
-                hap[2 * i], hap[2 * i + 1] = a, b
-    return hap
 
 
 def test_level_schedule_reproduces_gauss_seidel():
